@@ -28,10 +28,23 @@ Workloads (--workload):
           (--joined-split channels, the default), or the set split into
           subimages shared by the ranks like `tiled` (--joined-split subimages)
 
-At N = 1 the line also carries: tiled_n1 / joined_n1 (the split workloads
-and the unsplit C3 run on this GPU), c2_to_threshold, and cpu_baseline with a
+A plain run (`--gpus N --steps K --warmup W`) does what the headline figure
+needs and no more: it makes the inputs, runs W warm-up steps and K timed steps
+of the leg `value` comes from, writes that leg's outputs if `--dump-outputs
+DIR` is given, and prints the result line. Everything else is behind `--full`:
+the `perform_host_buffers` leg beside a resident headline, the HIP-event
+`roofline`, and at N = 1 tiled_n1 / joined_n1 (the split workloads and the
+unsplit C3 run on this GPU), c2_to_threshold, iuwt_c4 and cpu_baseline with a
 live to-threshold run of a smaller problem on the CPU and the GPU
-(`--to-threshold-live`, default t2k: 2048^2).
+(`--to-threshold-live`, default t2k: 2048^2). Those entries are null in a
+plain run's line.
+
+`--dump-outputs DIR`: after the timed steps, the residual and model images the
+last timed step left (what a caller of that step receives) and its component
+count go to DIR/residual.npy, DIR/model.npy (float32) and DIR/components.npy
+(float64). An image set above DUMP_MAX_ELEMS values is written as a fixed
+sample (dump_sample_index: sorted flat indices drawn with SEED), so two builds
+run with the same arguments write arrays that compare element for element.
 
 Multi-GPU: one process per GPU. `--gpus N` without a launcher re-launches
 itself under torch.distributed.run (before anything touches the GPU); under a
@@ -39,7 +52,7 @@ launcher WORLD_SIZE must equal N. Barrier + device sync bracket the timed
 region and the slowest rank's time is used; value = components of all ranks /
 that time.
 
-Also reported: `roofline` of the dominant kernel family (HIP events on the
+With `--full`, also reported: `roofline` of the dominant kernel family (HIP events on the
 stream of every session of the process, algorithmic bytes per SURVEY.md
 §8(d)) and `cpu_baseline` = the oracle (C++ restatement, std::thread, float64
 FFT) on a bounded sample of the same workload: its cleaning rate after setup,
@@ -152,6 +165,30 @@ def measured_traffic(family, bytes_per_launch):
         return None, None
     return (round(fam["traffic_over_algorithmic"] * bytes_per_launch),
             os.path.relpath(files[-1], ROOT))
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MB as float32
+
+
+def dump_sample_index(n):
+    """Flat indices of the dumped sample of an n-element output: all of them up
+    to DUMP_MAX_ELEMS, else DUMP_MAX_ELEMS sorted draws (with replacement) from
+    a generator seeded with SEED, the same in every run."""
+    if n <= DUMP_MAX_ELEMS:
+        return None
+    return np.sort(np.random.default_rng(SEED).integers(0, n, DUMP_MAX_ELEMS))
+
+
+def dump_outputs(dirname, arrays):
+    """Write every array of `arrays` (name -> ndarray) as dirname/<name>.npy,
+    float32 or float64, whole or as its dump_sample_index sample."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        idx = dump_sample_index(a.size)
+        np.save(os.path.join(dirname, name + ".npy"), a if idx is None else a.reshape(-1)[idx])
 
 
 def affinity_cores():
@@ -541,11 +578,33 @@ def main():
     ap.add_argument("--cpu-to-threshold-config", default="c2",
                     help="the tests/config_problems.py problem of --cpu-to-threshold (c2, "
                          "h8kt: the headline 8192^2 problem)")
-    ap.add_argument("--breakdown", action="store_true", help="per-kernel times to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline leg: the Radler.perform "
+                         "leg over host buffers, the HIP-event roofline and, at N = 1, the "
+                         "tiled / joined / C2 / C4 reference legs and the CPU baseline "
+                         "(each still has its own switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the residual and model of the last timed step and its "
+                         "component count as DIR/<name>.npy (large images: a fixed seeded "
+                         "sample)")
+    ap.add_argument("--breakdown", action="store_true",
+                    help="per-kernel times to stderr (needs --full)")
     ap.add_argument("--timing-all", action="store_true",
-                    help="count every launch of the process (PMC passes, tools/pmc_traffic.py)")
-    ap.add_argument("--dump-families", help="write the per-family launch/byte counts here")
+                    help="count every launch of the process (PMC passes, "
+                         "tools/pmc_traffic.py; needs --full)")
+    ap.add_argument("--dump-families",
+                    help="write the per-family launch/byte counts here (needs --full)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        for opt in ("breakdown", "timing_all", "dump_families"):
+            if getattr(args, opt):
+                ap.error(f"--{opt.replace('_', '-')} reads the HIP-event timing: add --full")
+        # a plain run: the headline leg alone
+        args.tiled_reference = args.joined_reference = args.iuwt_reference = 0
+        args.c2_reference = args.cpu_outer = 0
+        args.to_threshold_live = "none"
 
     if args.cpu_to_threshold:
         out = cpu_to_threshold(args.cpu_to_threshold_config, args.cpu_threads or cpu_share())
@@ -630,7 +689,7 @@ def main():
     if args.timing_all:
         timing.enable(True)
     print(f"[bench] rank {rank}: {workload} {args.size}^2 inputs ready; {args.warmup} warm-up "
-          f"+ {args.steps} timed Perform steps", file=sys.stderr, flush=True)
+          f"+ {args.steps} timed steps", file=sys.stderr, flush=True)
     # the N > 1 default workload (tiled 8 x 8) on this one GPU, the
     # same-workload reference point of the scaling curve
     tiled_ref = None
@@ -799,9 +858,13 @@ def main():
     # (RDL_SCALE_LANES=1, read per major iteration): on two lanes the
     # transforms of two scales overlap and each launch's event time includes
     # the other lane's share of HBM, which no per-kernel roofline can use.
+    # A plain run of a workload with a resident leg skips the Radler.perform
+    # leg (its warm-up and timed steps), and records no events at all.
+    has_resident = bool(args.device_resident) and not split
+    host_leg = args.full or not has_resident
     fams_all = None
-    for w in range(args.warmup):
-        profile = w == args.warmup - 1 and not args.timing_all
+    for w in range(args.warmup if host_leg else 0):
+        profile = args.full and w == args.warmup - 1 and not args.timing_all
         lanes_env = os.environ.get("RDL_SCALE_LANES")
         if profile:
             timing.reset()
@@ -820,15 +883,16 @@ def main():
                 os.environ["RDL_SCALE_LANES"] = lanes_env
     dominant = (max(fams_all.items(), key=lambda kv: kv[1]["ms"])[0]
                 if fams_all else None)
-    steps = [make_radler() for _ in range(args.steps)]
+    steps = [make_radler() for _ in range(args.steps if host_leg else 0)]
     if os.environ.get("RADLER_HOST_PROFILE") == "1":
         rd.gpu.host_profile_reset()  # the printed host profile covers the timed steps
 
     # the roofline's HIP events are recorded over the leg `value` comes from:
     # the HBM-resident DeviceRun leg when there is one, else these steps
-    has_resident = bool(args.device_resident) and not split
 
     def events_on():
+        if not args.full:
+            return
         if not args.timing_all:
             timing.reset()
             timing.only(dominant)
@@ -853,6 +917,11 @@ def main():
     fams = None
     if not has_resident:
         fams = events_off()
+    outputs = None
+    if args.dump_outputs and not has_resident and rank == 0:
+        _, o_residual, o_model = steps[-1][1]
+        outputs = {"residual": o_residual, "model": o_model,
+                   "components": np.array([rd.gpu.total_iteration_number(steps[-1][0])])}
     del steps
 
     # the same major iteration on an HBM-resident image set (no host transfers)
@@ -862,8 +931,10 @@ def main():
                                BEAM_PX * PIXEL_SCALE, trace=False)
         if comm is not None:
             run.set_communicator(comm)
-        run.restore()
-        run.execute()  # warm-up
+        # warm-up: the perform leg has warmed the kernels up when it ran
+        for _ in range(1 if host_leg else args.warmup):
+            run.restore()
+            run.execute()
         run.sync()
         events_on()
         barrier()
@@ -871,7 +942,8 @@ def main():
         rcomps = 0
         for _ in range(args.steps):
             run.restore()
-            rcomps += run.execute()["iterations"]
+            last_comps = run.execute()["iterations"]
+            rcomps += last_comps
         run.sync()
         barrier()
         relapsed = time.perf_counter() - t1
@@ -879,7 +951,15 @@ def main():
         resident = {"ms_per_step": round(1e3 * relapsed / args.steps, 2),
                     "components_per_step": rcomps // args.steps, "elapsed": relapsed,
                     "components": rcomps}
+        if args.dump_outputs and rank == 0:
+            shape = dirty.shape
+            outputs = {"residual": run.residual().reshape(shape),
+                       "model": run.model().reshape(shape),
+                       "components": np.array([last_comps])}
         del run
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
+        del outputs
     if args.dump_families and rank == 0:
         with open(args.dump_families, "w") as f:
             json.dump(fams, f, indent=1)
@@ -906,7 +986,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    ms_per_step = 1e3 * max_elapsed / args.steps
+    ms_per_step = 1e3 * max_elapsed / args.steps  # of the perform leg, when it ran
     # device-time shares from the every-family profile of the last warm-up
     # step (the timed steps record the dominant family only)
     prof = fams_all if fams_all else fams
@@ -1014,7 +1094,8 @@ def main():
             "value": round(total_comps / max_elapsed, 2),
             "components_per_step": total_comps // (args.steps * (1 if split or chan_shard
                                                                  else world)),
-            "step": "Radler.perform (accessor load over PCIe + major iteration + store)"}
+            "step": "Radler.perform (accessor load over PCIe + major iteration + store)"
+            } if host_leg else None
     if resident:
         v_value, v_ms = resident["value"], resident["ms_per_step"]
         v_comps = resident["components_per_step"]
@@ -1030,6 +1111,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": v_ms,
         "wall_clock_to_threshold_s": round(v_ms / 1e3, 4),
         "components_per_step": v_comps,

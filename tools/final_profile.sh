@@ -24,11 +24,11 @@ case $PASS in
     mkdir -p $OUT/$PASS
     cd /tmp && export TMPDIR=/tmp
     timeout -k 10 400 rocprofv3 --pmc $COUNTER --kernel-trace -d $OUT/$PASS -o run -- \
-      python3 $R/bench.py --warmup 0 --steps 1 --cpu-outer 0 --tiled-reference 0 --c2-reference 0 --joined-reference 0 --iuwt-reference 0 --device-resident 0 --timing-all \
+      python3 $R/bench.py --full --warmup 0 --steps 1 --cpu-outer 0 --tiled-reference 0 --c2-reference 0 --joined-reference 0 --iuwt-reference 0 --device-resident 0 --timing-all \
       --dump-families $OUT/$PASS/fams.json > $OUT/$PASS/bench.json 2> $OUT/$PASS/bench.err ;;
   bench)
     cd $R
-    timeout -k 10 600 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err ;;
+    timeout -k 10 600 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err ;;
   *)
     echo "unknown pass $PASS" >&2; exit 2 ;;
 esac

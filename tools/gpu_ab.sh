@@ -15,7 +15,7 @@ if [ -n "$TEST_FILES" ]; then
   [ $rc -le 1 ] || exit $rc
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 900 python -u bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} \
+  timeout -k 10 900 python -u bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5 --full} \
     > $OUT/bench.json 2> $OUT/bench.err || exit $?
   tail -1 $OUT/bench.json | cut -c1-300
 fi

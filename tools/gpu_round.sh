@@ -13,5 +13,5 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 840 python -u -m pytest ${GPU_TESTS:-tests} -m gpu -x -v --timeout 300 \
     --timeout-method thread -p no:cacheprovider -s > $OUT/gpu_tests.log 2>&1 || exit $?
 fi
-timeout -k 10 900 python -u bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} \
+timeout -k 10 900 python -u bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5 --full} \
   > $OUT/bench.json 2> $OUT/bench.err

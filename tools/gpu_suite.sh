@@ -12,6 +12,6 @@ rc=$?
 tail -5 $OUT/gpu_tests.log
 [ $rc -le 1 ] || exit $rc
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 900 python -u bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || exit $?
+  timeout -k 10 900 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err || exit $?
   tail -1 $OUT/bench.json | cut -c1-400
 fi

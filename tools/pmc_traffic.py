@@ -5,7 +5,7 @@ passes (MI355X_MICROARCH.md, "HBM" and "rocprofv3 PMC slots"):
   FETCH_SIZE and WRITE_SIZE do not fit one pass on gfx950, so each gets its
   own run of the same command:
     rocprofv3 --pmc FETCH_SIZE --kernel-trace -d D1 -o run -- python3 bench.py \
-        --warmup 0 --steps 1 --cpu-outer 0 --tiled-reference 0 --device-resident 0 --timing-all --dump-families D1/fams.json
+        --full --warmup 0 --steps 1 --cpu-outer 0 --tiled-reference 0 --device-resident 0 --timing-all --dump-families D1/fams.json
     rocprofv3 --pmc WRITE_SIZE ...  (same, into D2)
   then
     python tools/pmc_traffic.py D1/run_results.db D2/run_results.db D1/fams.json \
