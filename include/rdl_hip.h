@@ -325,7 +325,7 @@ typedef struct {
   uint32_t n_channels;  /* deconvolution channels (per polarization) */
   uint32_t n_terms;     /* 1 .. RDL_LOGPOLY_MAX_TERMS */
   uint32_t fit_mask;    /* bit c: channel c has weight > 0 and is fitted */
-  uint32_t reserved;
+  uint32_t flags;       /* 0, or RDL_LOGPOLY_FORCED (see rdl_forced_logpoly) */
   double lg[RDL_LOGPOLY_MAX_CHANNELS]; /* log10(nu_c / nu_ref) per channel */
 } rdl_logpoly;
 
@@ -338,6 +338,46 @@ int rdl_logpoly_interpolate(rdl_session* s, const float* d_in, size_t in_stride,
                             size_t n_pixels, const rdl_logpoly* fit,
                             const double* out_lg, uint32_t n_out, float* d_out,
                             size_t out_stride);
+
+/* ------------------------------------------------ forced spectral terms */
+/* SpectralFitter in kForcedTerms mode (WSClean's -force-spectrum): the shape
+ * terms t_1 .. t_{n_terms-1} of a component come from term planes at its
+ * pixel, and only the flux term is fitted:
+ *   f_c = 10^(t_1 lg_c + t_2 lg_c^2 + ...),  t_0 = sum w_c v_c / sum w_c f_c
+ * over the channels with w_c > 0 and finite v_c, f_c (0 when the divisor is
+ * zero or not finite); the fitted values are t_0 f_c (csrc/hip/logpoly.h).
+ * It goes with an rdl_logpoly, which supplies n_channels, n_terms and lg
+ * (rdl_forced_logpoly below joins the two for the loops). d_planes holds n_terms - 1 device planes of `rows` rows
+ * of `pitch` floats (plane k at d_planes + k * plane_stride); pixel (x, y)
+ * of the image a call works on is pixel (x + x0, y + y0) of the planes, so a
+ * subimage passes the full planes and its origin. */
+typedef struct {
+  const float* d_planes;   /* may be NULL when n_terms == 1 */
+  size_t plane_stride;     /* floats between planes, >= pitch * rows */
+  uint32_t pitch, rows;    /* size of a plane */
+  uint32_t x0, y0;         /* origin of the image inside the planes */
+  float weights[RDL_LOGPOLY_MAX_CHANNELS]; /* w_c per channel */
+} rdl_forced_terms;
+
+/* How the Högbom and sub-minor loops receive a forced-term fit: their
+ * params' `logpoly` points at the `fit` member of this struct, and
+ * fit.flags has RDL_LOGPOLY_FORCED set to say that `terms` follows. The
+ * params structs themselves keep their layout, so a caller built against
+ * them before forced terms existed (flags = 0) is read as before. */
+#define RDL_LOGPOLY_FORCED 1u
+typedef struct {
+  rdl_logpoly fit;
+  rdl_forced_terms terms;
+} rdl_forced_logpoly;
+
+/* ImageSet::InterpolateAndStoreModel for forced-term fitting, one
+ * polarization: as rdl_logpoly_interpolate on a width x height image (plane
+ * c at d_in + c * in_stride), every non-zero pixel fitted with the terms of
+ * its own position and evaluated at out_lg[g] (zero pixels give zero). */
+int rdl_forced_interpolate(rdl_session* s, const float* d_in, size_t in_stride,
+                           uint32_t width, uint32_t height, const rdl_logpoly* fit,
+                           const rdl_forced_terms* forced, const double* out_lg,
+                           uint32_t n_out, float* d_out, size_t out_stride);
 
 /* ---------------------------------------------------------------- Högbom */
 typedef struct {
@@ -366,7 +406,8 @@ typedef struct {
    * every peak search, generic_clean.cc:255-264); NULL = none */
   const float* d_rms;
   /* log-polynomial PerformSpectralFit instead of d_spectral (host pointer,
-   * copied at the call; NULL = none) */
+   * copied at the call; NULL = none); with RDL_LOGPOLY_FORCED in its flags
+   * it is the head of an rdl_forced_logpoly: the forced-term fit */
   const rdl_logpoly* logpoly;
 } rdl_hogbom_params;
 
@@ -409,7 +450,10 @@ typedef struct {
    * NULL = none */
   const float* d_rms;
   /* log-polynomial PerformSpectralFit of each component's gain-scaled values
-   * instead of d_spectral (host pointer, copied at the call; NULL = none) */
+   * instead of d_spectral (host pointer, copied at the call; NULL = none);
+   * with RDL_LOGPOLY_FORCED in its flags it is the head of an
+   * rdl_forced_logpoly: the forced-term fit. Both run in the LDS-resident
+   * loop only. */
   const rdl_logpoly* logpoly;
 } rdl_subminor_params;
 

@@ -88,6 +88,8 @@ struct HogbomArgs {
   int32_t allow_negative, stop_on_negative;
   rdl_logpoly lp;  // log-polynomial fit (has_lp), instead of spectral
   int32_t has_lp;
+  int32_t has_forced;  // forced-term fit with lp's channels (needs has_lp)
+  rdl_forced_terms forced;
 };
 
 // Iteration pass: subtract the current component from every image inside its
@@ -170,7 +172,13 @@ __device__ void HogbomPrepare(const HogbomArgs& a, HogbomState& st) {
   if (a.has_lp) {  // log-polynomial PerformSpectralFit before the gain
     float v[RDL_MAX_IMAGES];
     for (uint32_t i = 0; i < a.n_images; ++i) v[i] = a.residuals[size_t(i) * n + idx];
-    lp::PerformSpectralFit(a.lp, a.n_pol, v);
+    if (a.has_forced) {  // with the terms of the peak's own pixel
+      float terms[lp::kMaxTerms];
+      lp::LoadForcedTerms(a.forced, a.lp.n_terms, idx % a.width, idx / a.width, terms);
+      lp::PerformForcedFit(a.lp, a.forced.weights, terms, a.n_pol, v);
+    } else {
+      lp::PerformSpectralFit(a.lp, a.n_pol, v);
+    }
     for (uint32_t i = 0; i < a.n_images; ++i) {
       const float f = v[i] * a.gain;
       st.factors[i] = f;
@@ -274,6 +282,13 @@ int rdl_hogbom_run(rdl_session* s, float* d_residuals, float* d_models,
                   "log-polynomial fit does not match the images");
     a.lp = *p->logpoly;
     a.has_lp = 1;
+  }
+  if (const rdl_forced_terms* forced = rdl::lp::ForcedTermsOf(p->logpoly)) {
+    RDL_ARG_CHECK(rdl::lp::ForcedTermsCover(*forced, p->logpoly->n_terms, p->width,
+                                            p->height),
+                  "forced-term planes do not cover the image");
+    a.forced = *forced;
+    a.has_forced = 1;
   }
   a.width = p->width;
   a.height = p->height;

@@ -244,5 +244,89 @@ RDL_HD inline void PerformSpectralFit(const rdl_logpoly& f, uint32_t n_pol, floa
   }
 }
 
+// ------------------------------------------------------------ forced terms
+// SpectralFitter in kForcedTerms mode (schaapcommon's forced-term fit behind
+// WSClean's -force-spectrum; not vendored either, so this too is a
+// restatement with unpinned parity — DESIGN.md). The shape terms t_1 ..
+// t_{n-1} of a spectrum are given (read from term planes at the component's
+// pixel); only the flux term is fitted:
+//   f_c = 10^(t_1 lg_c + t_2 lg_c^2 + ...)         (Exponent / Evaluate above)
+//   t_0 = sum_c w_c v_c / sum_c w_c f_c   over w_c > 0 with finite v_c, f_c
+//   t_0 = 0 when the divisor is zero or not finite.
+// This is the weighted-mean estimate, not least squares: the weighted sum of
+// the fitted values equals that of the data, so the integrated peak a CLEAN
+// loop follows keeps falling. Double, fixed order; t_0 is rounded to float
+// before the evaluation, as Fit() returns float terms.
+
+RDL_HD inline bool Finite(double v) { return v - v == 0.0; }
+
+// terms[0] of the spectrum `values` for the given terms[1..n_terms);
+// shape[c] receives f_c
+RDL_HD inline float ForcedFit(const rdl_logpoly& f, const float* weights, const float* terms,
+                              const float* values, double* shape) {
+  const int n_terms = int(f.n_terms);
+  double num = 0.0, den = 0.0;
+  for (int c = 0; c < int(f.n_channels); ++c) {
+    double e = 0.0;
+    for (int k = n_terms - 1; k >= 1; --k) e = (e + double(terms[k])) * f.lg[c];
+    shape[c] = exp(kLn10 * e);
+    const double w = double(weights[c]), v = double(values[c]);
+    if (w > 0.0 && Finite(v) && Finite(shape[c])) {
+      num += w * v;
+      den += w * shape[c];
+    }
+  }
+  if (den == 0.0 || !Finite(den)) return 0.0f;
+  return float(num / den);
+}
+
+// SpectralFitter::FitAndEvaluate in forced mode on one channel spectrum, in
+// place (the value Evaluate() gives for the terms {t_0, terms[1], ...})
+RDL_HD inline void ForcedFitAndEvaluate(const rdl_logpoly& f, const float* weights,
+                                        const float* terms, float* values) {
+  double shape[kMaxCh];
+  const float t0 = ForcedFit(f, weights, terms, values, shape);
+  for (int c = 0; c < int(f.n_channels); ++c) values[c] = float(double(t0) * shape[c]);
+}
+
+// PerformSpectralFit in forced mode: values ordered [channel][pol]; every
+// polarization is fitted with the same terms (those of the pixel)
+RDL_HD inline void PerformForcedFit(const rdl_logpoly& f, const float* weights,
+                                    const float* terms, uint32_t n_pol, float* values) {
+  for (uint32_t p = 0; p < n_pol; ++p) {
+    float ch[kMaxCh];
+    for (uint32_t c = 0; c < f.n_channels; ++c) ch[c] = values[c * n_pol + p];
+    ForcedFitAndEvaluate(f, weights, terms, ch);
+    for (uint32_t c = 0; c < f.n_channels; ++c) values[c * n_pol + p] = ch[c];
+  }
+}
+
+// Whether every pixel of a width x height image lies inside the planes (the
+// entry points check it before a kernel reads them)
+inline bool ForcedTermsCover(const rdl_forced_terms& t, uint32_t n_terms, uint32_t width,
+                             uint32_t height) {
+  if (n_terms <= 1) return true;
+  return t.d_planes != nullptr && uint64_t(t.x0) + width <= t.pitch &&
+         uint64_t(t.y0) + height <= t.rows &&
+         uint64_t(t.pitch) * t.rows <= t.plane_stride;
+}
+
+// The forced terms that follow a loop's rdl_logpoly (rdl_forced_logpoly), or
+// nullptr for a plain log-polynomial fit
+inline const rdl_forced_terms* ForcedTermsOf(const rdl_logpoly* fit) {
+  if (!fit || !(fit->flags & RDL_LOGPOLY_FORCED)) return nullptr;
+  return &reinterpret_cast<const rdl_forced_logpoly*>(fit)->terms;
+}
+
+#if defined(__HIPCC__)
+// terms[1..n_terms) of pixel (x, y) of the image a loop works on
+__device__ inline void LoadForcedTerms(const rdl_forced_terms& t, uint32_t n_terms, uint32_t x,
+                                       uint32_t y, float* terms) {
+  const size_t i = size_t(y + t.y0) * t.pitch + (x + t.x0);
+  terms[0] = 0.0f;
+  for (uint32_t k = 1; k < n_terms; ++k) terms[k] = t.d_planes[size_t(k - 1) * t.plane_stride + i];
+}
+#endif
+
 }  // namespace lp
 }  // namespace rdl

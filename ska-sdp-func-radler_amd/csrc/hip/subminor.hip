@@ -562,6 +562,8 @@ struct LoopArgs {
   const float* table;     // pairwise PSF table (BuildPairTable) or nullptr
   rdl_logpoly lp;         // log-polynomial fit (has_lp; SubminorLoop only)
   int32_t has_lp;
+  int32_t has_forced;     // forced-term fit with lp's channels (needs has_lp)
+  rdl_forced_terms forced;
   // table loops on a grid: launched blocks per participant (the participants
   // are blocks 0, S, 2S, ...: S = 8 puts them on one XCD under round-robin
   // dispatch; a pooled session whose share of the GPU is below 8 blocks per
@@ -829,7 +831,18 @@ __global__ __launch_bounds__(kLoopThreads) void SubminorLoop(LoopArgs a) {
       float v[NI];
       for (int k = 0; k < NI; ++k)
         v[k] = k < int(n_img) ? __uint_as_float(win[4 + k]) * a.gain : 0.0f;
-      lp::PerformSpectralFit(a.lp, a.n_pol, v);
+      if (a.has_forced) {
+        // forced terms of the winner's pixel: one address for the whole
+        // workgroup, so the loads and the fit stay wave-uniform
+        float terms[lp::kMaxTerms];
+        const uint32_t wx = win[3] & 0xffffu, wy = win[3] >> 16;
+        for (int k = 0; k < lp::kMaxTerms; ++k) terms[k] = 0.0f;
+        if (wx < a.width && wy < a.height)  // (the planes cover the image: checked at launch)
+          lp::LoadForcedTerms(a.forced, a.lp.n_terms, wx, wy, terms);
+        lp::PerformForcedFit(a.lp, a.forced.weights, terms, a.n_pol, v);
+      } else {
+        lp::PerformSpectralFit(a.lp, a.n_pol, v);
+      }
 #pragma unroll
       for (int k = 0; k < NI; ++k) c[k] = k < int(n_img) ? v[k] : 0.0f;
     } else if (a.spectral) {
@@ -2793,6 +2806,10 @@ int SubminorLaunch(rdl_subminor* h, const float* d_residuals, const float* d_psf
                                 p->logpoly->n_terms >= 1 &&
                                 p->logpoly->n_terms <= RDL_LOGPOLY_MAX_TERMS),
                 "log-polynomial fit does not match the images");
+  const rdl_forced_terms* forced = rdl::lp::ForcedTermsOf(p->logpoly);
+  RDL_ARG_CHECK(!forced || rdl::lp::ForcedTermsCover(*forced, p->logpoly->n_terms, p->width,
+                                                     p->height),
+                "forced-term planes do not cover the image");
   RDL_ARG_CHECK(p->width > 0 && p->height > 0 && p->width <= 65535 &&
                     p->height <= 65535,
                 "image size out of range (1..65535)");
@@ -3133,6 +3150,10 @@ int SubminorLaunch(rdl_subminor* h, const float* d_residuals, const float* d_psf
   if (lpfit) {
     la.lp = *p->logpoly;
     la.has_lp = 1;
+    if (forced) {
+      la.forced = *forced;
+      la.has_forced = 1;
+    }
   }
   la.divergence_limit = p->divergence_limit;
   la.iteration_start = p->iteration_start;

@@ -156,6 +156,18 @@ class ImageAccessor {
   virtual void Store(const float* data) = 0;
 };
 
+// aocommon/imagecoordinates.h: the direction cosines of pixel (x, y); l
+// grows to the left of the image centre, m upwards
+struct ImageCoordinates {
+  template <typename T>
+  static void XYToLM(size_t x, size_t y, T pixel_size_x, T pixel_size_y, size_t width,
+                     size_t height, T& l, T& m) {
+    const T mid_x = T(width) / T(2), mid_y = T(height) / T(2);
+    l = (mid_x - T(x)) * pixel_size_x;
+    m = (T(y) - mid_y) * pixel_size_y;
+  }
+};
+
 }  // namespace aocommon
 
 namespace schaapcommon::fitters {

@@ -1,8 +1,73 @@
 #include "deconvolution_algorithm.h"
 
 #include <stdexcept>
+#include <string>
+
+#include "logpoly.h"
 
 namespace radler::algorithms {
+
+void DeconvolutionAlgorithm::SetSpectrallyForcedImages(
+    std::vector<std::vector<float>> planes, size_t width) {
+  if (!has_forced_)
+    throw std::runtime_error(
+        "SetSpectrallyForcedImages: the spectral fitter is not in forced-terms mode");
+  const uint32_t n_terms = forced_.fit.n_terms;
+  if (planes.size() + 1 != n_terms)
+    throw std::runtime_error("SetSpectrallyForcedImages: " + std::to_string(planes.size()) +
+                             " term planes given, a fit of " + std::to_string(n_terms) +
+                             " terms needs " + std::to_string(n_terms - 1));
+  auto images = std::make_shared<ForcedTermImages>();
+  images->n_planes = planes.size();
+  images->width = width;
+  for (const std::vector<float>& p : planes) {
+    if (width == 0 || p.empty() || p.size() != planes.front().size() || p.size() % width != 0)
+      throw std::runtime_error(
+          "SetSpectrallyForcedImages: the term planes must be non-empty, of equal size and "
+          "made of rows of the given width");
+    images->height = p.size() / width;
+    images->data.insert(images->data.end(), p.begin(), p.end());
+  }
+  SetSpectrallyForcedImages(std::move(images), 0, 0);
+}
+
+const rdl_logpoly* DeconvolutionAlgorithm::DeviceFit(gpu::Session& s, size_t width,
+                                                     size_t height) {
+  if (!has_forced_) return LogPolyFit();
+  const rdl_logpoly& fit = forced_.fit;
+  rdl_forced_terms& terms = forced_.terms;
+  forced_.fit.flags = RDL_LOGPOLY_FORCED;
+  terms.d_planes = nullptr;
+  terms.plane_stride = 0;
+  terms.pitch = terms.rows = terms.x0 = terms.y0 = 0;
+  if (fit.n_terms <= 1) return &forced_.fit;
+  if (!forced_images_)
+    throw std::runtime_error(
+        "Forced-term spectral fitting needs term images (SetSpectrallyForcedImages)");
+  const ForcedTermImages& im = *forced_images_;
+  if (im.n_planes + 1 != fit.n_terms || forced_x0_ + width > im.width ||
+      forced_y0_ + height > im.height || im.data.size() != im.n_planes * im.width * im.height)
+    throw std::runtime_error(
+        "The forced spectral-term images do not cover the deconvolved image");
+  if (!forced_device_ || forced_device_session_ != &s) {
+    forced_device_ = std::make_shared<gpu::Buffer>(s, im.data.size() * sizeof(float));
+    s.H2D(forced_device_->Ptr(), im.data.data(), im.data.size() * sizeof(float));
+    forced_device_session_ = &s;
+  }
+  terms.d_planes = forced_device_->F();
+  terms.plane_stride = im.width * im.height;
+  terms.pitch = uint32_t(im.width);
+  terms.rows = uint32_t(im.height);
+  terms.x0 = uint32_t(forced_x0_);
+  terms.y0 = uint32_t(forced_y0_);
+  return &forced_.fit;
+}
+
+void DeconvolutionAlgorithm::RejectForcedTermsForOptimization() const {
+  if (has_forced_)
+    throw std::runtime_error(
+        "Component optimization cannot be combined with forced-term spectral fitting");
+}
 
 const uint8_t* DeconvolutionAlgorithm::DeviceCleanMask(gpu::Session& s,
                                                        size_t width,
@@ -21,6 +86,27 @@ const uint8_t* DeconvolutionAlgorithm::DeviceCleanMask(gpu::Session& s,
 void DeconvolutionAlgorithm::PerformSpectralFit(float* values, size_t x,
                                                 size_t y) const {
   if (!spectral_fitter_) return;
+  if (has_forced_) {
+    // the terms of the pixel inside the full-image planes (the shared fitter
+    // holds no planes: each subimage algorithm has its own origin)
+    const rdl_logpoly& fit = forced_.fit;
+    float terms[RDL_LOGPOLY_MAX_TERMS] = {};
+    if (fit.n_terms > 1) {
+      if (!forced_images_)
+        throw std::runtime_error(
+            "Forced-term spectral fitting needs term images (SetSpectrallyForcedImages)");
+      const ForcedTermImages& im = *forced_images_;
+      const size_t px = x + forced_x0_, py = y + forced_y0_;
+      if (px >= im.width || py >= im.height || im.n_planes + 1 != fit.n_terms)
+        throw std::runtime_error(
+            "The forced spectral-term images do not cover the deconvolved image");
+      for (size_t k = 1; k != fit.n_terms; ++k)
+        terms[k] = im.data[((k - 1) * im.height + py) * im.width + px];
+    }
+    rdl::lp::PerformForcedFit(fit, forced_.terms.weights, terms, uint32_t(n_polarizations_),
+                              values);
+    return;
+  }
   const size_t n = spectral_fitter_->Frequencies().size();
   std::vector<float> channel(n), scratch;
   for (size_t p = 0; p != n_polarizations_; ++p) {

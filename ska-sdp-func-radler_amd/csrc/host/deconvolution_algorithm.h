@@ -91,7 +91,25 @@ class DeconvolutionAlgorithm {
     n_polarizations_ = n_polarizations;
     spectral_map_.reset();
     has_logpoly_ = spectral_fitter_ && MakeLogPoly(*spectral_fitter_, &logpoly_);
+    has_forced_ = !has_logpoly_ && spectral_fitter_ &&
+                  MakeForcedLogPoly(*spectral_fitter_, &forced_.fit, forced_.terms.weights);
   }
+  /// deconvolution_algorithm.h:155 — the term planes of a kForcedTerms fitter
+  /// (NTerms() - 1 planes of equal size, rows of `width` floats).
+  void SetSpectrallyForcedImages(std::vector<std::vector<float>> planes, size_t width);
+  /// The same with shared full-image planes; (x0, y0) is the origin inside
+  /// them of the image this algorithm deconvolves (a grid's subimage).
+  void SetSpectrallyForcedImages(std::shared_ptr<const ForcedTermImages> planes,
+                                 size_t x0 = 0, size_t y0 = 0) {
+    if (planes != forced_images_) forced_device_.reset();  // the origin is not in the copy
+    forced_images_ = std::move(planes);
+    forced_x0_ = x0;
+    forced_y0_ = y0;
+  }
+  const std::shared_ptr<const ForcedTermImages>& SpectrallyForcedImages() const {
+    return forced_images_;
+  }
+  bool HasForcedTerms() const { return has_forced_; }
   const schaapcommon::fitters::SpectralFitter& Fitter() const {
     return *spectral_fitter_;
   }
@@ -122,6 +140,11 @@ class DeconvolutionAlgorithm {
         n_polarizations_(o.n_polarizations_),
         logpoly_(o.logpoly_),
         has_logpoly_(o.has_logpoly_),
+        has_forced_(o.has_forced_),
+        forced_(o.forced_),
+        forced_images_(o.forced_images_),
+        forced_x0_(o.forced_x0_),
+        forced_y0_(o.forced_y0_),
         rms_factor_(o.rms_factor_),
         record_trace_(o.record_trace_) {}
 
@@ -139,6 +162,15 @@ class DeconvolutionAlgorithm {
   /// (rdl_subminor_params / rdl_hogbom_params logpoly), or nullptr for the
   /// other modes (which DeviceSpectralMap covers).
   const rdl_logpoly* LogPolyFit() const { return has_logpoly_ ? &logpoly_ : nullptr; }
+  /// The fit the device loops on a width x height image take as their
+  /// params' logpoly: LogPolyFit(), or for a forced-term fitter the head of
+  /// an rdl_forced_logpoly (flags = RDL_LOGPOLY_FORCED) whose term planes are
+  /// on session s (the device copy is cached per session); nullptr for the
+  /// other modes. Throws when the fitter is in forced mode and no planes
+  /// cover the image.
+  const rdl_logpoly* DeviceFit(gpu::Session& s, size_t width, size_t height);
+  /// Component optimisation has no defined meaning with forced terms.
+  void RejectForcedTermsForOptimization() const;
   /// Device copy of RmsFactorImage() on session s, or nullptr.
   const float* DeviceRmsFactor(gpu::Session& s, size_t width, size_t height);
   /// The peak-search input: d_image itself, or d_image x the RMS factor in
@@ -171,6 +203,13 @@ class DeconvolutionAlgorithm {
   size_t n_polarizations_ = 1;
   rdl_logpoly logpoly_{};
   bool has_logpoly_ = false;
+  // kForcedTerms: forced_.fit describes the channels, forced_.terms the planes
+  bool has_forced_ = false;
+  rdl_forced_logpoly forced_{};
+  std::shared_ptr<const ForcedTermImages> forced_images_;
+  size_t forced_x0_ = 0, forced_y0_ = 0;
+  std::shared_ptr<gpu::Buffer> forced_device_;
+  gpu::Session* forced_device_session_ = nullptr;
   std::shared_ptr<gpu::Buffer> spectral_map_;
   size_t spectral_map_images_ = 0;
   gpu::Session* spectral_map_session_ = nullptr;

@@ -2,6 +2,7 @@
 
 #include <stdexcept>
 
+#include "fits_image.h"
 #include "generic_clean.h"
 #include "image_accessors.h"
 #include "iuwt_deconvolution.h"
@@ -87,9 +88,6 @@ DeviceRun::DeviceRun(const Settings& settings, const float* psf,
      // 100 MHz + c x 10 MHz
     using schaapcommon::fitters::SpectralFittingMode;
     const SpectralFittingMode mode = settings.spectral_fitting.mode;
-    if (mode == SpectralFittingMode::kForcedTerms)
-      throw std::runtime_error(
-          "DeviceRun: forced-term spectral fitting is not available");
     std::vector<double> frequencies;
     std::vector<float> channel_weights;
     if (mode != SpectralFittingMode::kNoFitting)
@@ -102,6 +100,22 @@ DeviceRun::DeviceRun(const Settings& settings, const float* psf,
   }
   parallel_ = std::make_unique<algorithms::ParallelDeconvolution>(settings_);
   parallel_->SetAlgorithm(std::move(algorithm));
+  if (settings.spectral_fitting.mode ==
+      schaapcommon::fitters::SpectralFittingMode::kForcedTerms) {
+    // Radler::ReadForcedSpectrumImages (radler.cc:410-432)
+    FitsImageReader reader(settings.spectral_fitting.forced_filename, "Forced spectrum file");
+    if (reader.Width() != w || reader.Height() != h)
+      throw std::runtime_error(
+          "The image dimensions of the forced spectrum fits file do not match "
+          "the deconvolved image dimensions");
+    if (reader.NImages() + 1 != settings.spectral_fitting.terms)
+      throw std::runtime_error(
+          "The number of images in the forced spectrum fits file does not match "
+          "the deconvolved image dimensions");
+    std::vector<std::vector<float>> terms(reader.NImages(), std::vector<float>(n));
+    for (size_t t = 0; t != terms.size(); ++t) reader.ReadIndex(terms[t].data(), t);
+    parallel_->SetSpectrallyForcedImages(std::move(terms), w);
+  }
   Restore();
   s.Sync();
 }

@@ -7,6 +7,7 @@
 
 #include "component_optimization.h"
 #include "logger.h"
+#include "logpoly.h"
 #include "subminor.h"
 
 namespace radler::algorithms {
@@ -66,16 +67,24 @@ void GenericClean::FitSpectra(ImageSet& model_set) {
   // the per-component matrix)
   gpu::Session& s = model_set.Session();
   const size_t n_img = model_set.Size(), n = model_set.Width() * model_set.Height();
-  if (const rdl_logpoly* lp = LogPolyFit()) {
+  if (const rdl_logpoly* lp = DeviceFit(s, model_set.Width(), model_set.Height())) {
     // the non-linear fit per pixel and polarization, evaluated at the
     // deconvolution channels themselves
     const size_t n_pol = model_set.NPolarizations();
     const std::vector<double> lg(lp->lg, lp->lg + lp->n_channels);
+    const rdl_forced_terms* forced = rdl::lp::ForcedTermsOf(lp);
     gpu::Buffer out(s, lp->n_channels * n * sizeof(float));
     for (size_t p = 0; p != n_pol; ++p) {
-      gpu::Check(rdl_logpoly_interpolate(s.Handle(), model_set.Data(p), n_pol * n, n, lp,
-                                         lg.data(), lp->n_channels, out.F(), n),
-                 "rdl_logpoly_interpolate");
+      if (forced)
+        gpu::Check(rdl_forced_interpolate(s.Handle(), model_set.Data(p), n_pol * n,
+                                          uint32_t(model_set.Width()),
+                                          uint32_t(model_set.Height()), lp, forced, lg.data(),
+                                          lp->n_channels, out.F(), n),
+                   "rdl_forced_interpolate");
+      else
+        gpu::Check(rdl_logpoly_interpolate(s.Handle(), model_set.Data(p), n_pol * n, n, lp,
+                                           lg.data(), lp->n_channels, out.F(), n),
+                   "rdl_logpoly_interpolate");
       for (size_t c = 0; c != lp->n_channels; ++c)
         s.D2D(model_set.Data(c * n_pol + p), out.F() + c * n, n * sizeof(float));
     }
@@ -121,6 +130,7 @@ DeconvolutionResult GenericClean::ExecuteMajorIteration(
   if (IterationNumber() >= MaxIterations()) return result;
   if (ComponentOptimizationAlgorithm() != OptimizationAlgorithm::kClean) {  // :89-95
     log::Info() << "Running optimization algorithm...\n";
+    RejectForcedTermsForOptimization();
     RunComponentOptimization(dirty_set, model_set, psfs);
     FitSpectra(model_set);
     return result;
@@ -143,7 +153,7 @@ DeconvolutionResult GenericClean::ExecuteMajorIteration(
     sub.SetDivergenceLimit(DivergenceLimit());
     sub.SetMask(d_mask);
     sub.SetSpectralMap(DeviceSpectralMap(s, dirty_set.Size()));
-    sub.SetLogPolyFit(LogPolyFit());
+    sub.SetLogPolyFit(DeviceFit(s, width, height));
     sub.SetRmsFactor(DeviceRmsFactor(s, width, height));  // :126-128
     sub.SetCleanBorders(size_t(std::round(width * CleanBorderRatio())),
                         size_t(std::round(height * CleanBorderRatio())));
@@ -186,7 +196,7 @@ DeconvolutionResult GenericClean::ExecuteMajorIteration(
     p.v_border = uint32_t(std::round(height * CleanBorderRatio()));
     p.d_mask = d_mask;
     p.d_spectral = DeviceSpectralMap(s, dirty_set.Size());
-    p.logpoly = LogPolyFit();
+    p.logpoly = DeviceFit(s, width, height);
     p.d_rms = DeviceRmsFactor(s, width, height);
     p.start_x = max_value.x;
     p.start_y = max_value.y;

@@ -290,7 +290,7 @@ void ImageSet::AssignAndStoreResidual() {  // image_set.cc:290-307
 }
 
 void ImageSet::InterpolateAndStoreModel(
-    const schaapcommon::fitters::SpectralFitter* fitter) {
+    const schaapcommon::fitters::SpectralFitter* fitter, const ForcedTermImages* forced) {
   // image_set.cc:209-288
   float* host = static_cast<float*>(session_->PinnedStaging(PlaneSize() * sizeof(float)));
   if (NDeconvolutionChannels() == NOriginalChannels()) {
@@ -303,7 +303,23 @@ void ImageSet::InterpolateAndStoreModel(
     return;
   }
   rdl_logpoly lp;
-  if (fitter && MakeLogPoly(*fitter, &lp)) {
+  rdl_forced_terms terms{};
+  const bool forced_mode = fitter && MakeForcedLogPoly(*fitter, &lp, terms.weights);
+  gpu::Buffer term_planes;
+  if (forced_mode && lp.n_terms > 1) {
+    if (!forced || forced->n_planes + 1 != lp.n_terms || forced->width != Width() ||
+        forced->height != Height() || forced->data.size() != forced->n_planes * PlaneSize())
+      throw std::runtime_error(
+          "InterpolateAndStoreModel: forced-term fitting needs term images of the image "
+          "set's size, one per term after the first");
+    term_planes = gpu::Buffer(*session_, forced->data.size() * sizeof(float));
+    session_->H2D(term_planes.Ptr(), forced->data.data(), forced->data.size() * sizeof(float));
+    terms.d_planes = term_planes.F();
+    terms.plane_stride = PlaneSize();
+    terms.pitch = uint32_t(Width());
+    terms.rows = uint32_t(Height());
+  }
+  if (forced_mode || (fitter && MakeLogPoly(*fitter, &lp))) {
     // the non-linear fit per non-zero pixel (image_set.cc:238-268), evaluated
     // at every original channel of the polarization (:270-285)
     if (lp.n_channels != NDeconvolutionChannels())
@@ -319,10 +335,17 @@ void ImageSet::InterpolateAndStoreModel(
         for (size_t g = g0; g != g0 + n_out; ++g)
           out_lg.push_back(std::log10(table_.OriginalGroups()[g][p]->CentralFrequency() /
                                       fitter->ReferenceFrequency()));
-        gpu::Check(rdl_logpoly_interpolate(session_->Handle(), Data(p), n_pol_ * PlaneSize(),
-                                           PlaneSize(), &lp, out_lg.data(), uint32_t(n_out),
-                                           out.F(), PlaneSize()),
-                   "rdl_logpoly_interpolate");
+        if (forced_mode)
+          gpu::Check(rdl_forced_interpolate(session_->Handle(), Data(p), n_pol_ * PlaneSize(),
+                                            uint32_t(Width()), uint32_t(Height()), &lp, &terms,
+                                            out_lg.data(), uint32_t(n_out), out.F(),
+                                            PlaneSize()),
+                     "rdl_forced_interpolate");
+        else
+          gpu::Check(rdl_logpoly_interpolate(session_->Handle(), Data(p), n_pol_ * PlaneSize(),
+                                             PlaneSize(), &lp, out_lg.data(), uint32_t(n_out),
+                                             out.F(), PlaneSize()),
+                     "rdl_logpoly_interpolate");
         for (size_t g = g0; g != g0 + n_out; ++g) {
           session_->D2H(host, out.F() + (g - g0) * PlaneSize(), PlaneSize() * sizeof(float));
           table_.OriginalGroups()[g][p]->model_accessor->Store(host);

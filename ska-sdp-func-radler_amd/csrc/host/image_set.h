@@ -41,9 +41,11 @@ class ImageSet {
   /// than original channels, every original channel receives the fit over
   /// the deconvolution channels evaluated at its central frequency
   /// (rdl_spectral_interpolate); without one (kNoFitting), the model of the
-  /// deconvolution channel it was averaged into.
+  /// deconvolution channel it was averaged into. A kForcedTerms fitter
+  /// needs `forced`, the full-image term planes (rdl_forced_interpolate).
   void InterpolateAndStoreModel(
-      const schaapcommon::fitters::SpectralFitter* fitter = nullptr);
+      const schaapcommon::fitters::SpectralFitter* fitter = nullptr,
+      const ForcedTermImages* forced = nullptr);
 
   void GetLinearIntegrated(float* d_dest) const;
   void GetSquareIntegrated(float* d_dest) const;

@@ -516,6 +516,7 @@ DeconvolutionResult MultiScaleAlgorithm::ExecuteMajorIteration(
     }
   } mask_sync{this};
   if (ComponentOptimizationAlgorithm() != OptimizationAlgorithm::kClean) {  // :242-246
+    RejectForcedTermsForOptimization();
     RunFullComponentFitter(data_image, model_image, psfs);
     return DeconvolutionResult{};
   }
@@ -707,7 +708,7 @@ DeconvolutionResult MultiScaleAlgorithm::ExecuteMajorIteration(
                            scale_border));
       sub.SetMask(MaskFor(scale_with_peak));
       sub.SetSpectralMap(DeviceSpectralMap(session, data_image.Size()));
-      sub.SetLogPolyFit(LogPolyFit());
+      sub.SetLogPolyFit(DeviceFit(session, width, height));
       sub.SetRmsFactor(DeviceRmsFactor(session, width, height));  // :401-402
       std::vector<uint32_t> xy;
       if (RecordTrace()) sub.SetTrace(&xy);

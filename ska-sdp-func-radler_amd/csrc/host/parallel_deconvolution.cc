@@ -140,6 +140,14 @@ void ParallelDeconvolution::SetRmsFactorImage(
   }
 }
 
+void ParallelDeconvolution::SetSpectrallyForcedImages(
+    std::vector<std::vector<float>> planes, size_t width) {
+  // the first algorithm validates and packs the planes; the others share them
+  algorithms_.front()->SetSpectrallyForcedImages(std::move(planes), width);
+  if (algorithms_.size() != 1)
+    forced_images_ = algorithms_.front()->SpectrallyForcedImages();
+}
+
 void ParallelDeconvolution::SetCleanMask(const bool* mask) {
   if (algorithms_.size() == 1)
     algorithms_.front()->SetCleanMask(mask);
@@ -473,6 +481,8 @@ bool ParallelDeconvolution::DeconvolveSubImage(SubImage& sub, ImageSet& sub_data
                   sub_rms->data() + y * sub.width);
     alg.SetRmsFactorImage(std::move(sub_rms));
   }
+  // the full-image term planes with this subimage's origin (:340-349)
+  if (forced_images_) alg.SetSpectrallyForcedImages(forced_images_, sub.x, sub.y);
   const size_t max_n_iter = alg.MaxIterations();
   if (find_peak_only)
     alg.SetMaxIterations(0);

@@ -59,6 +59,12 @@ class ParallelDeconvolution {
   /// is; gridded runs trim each subimage's box (:332-337) and drop it after
   /// the run (:421-423). nullptr clears it.
   void SetRmsFactorImage(std::shared_ptr<const std::vector<float>> image, size_t width);
+  /// parallel_deconvolution.cc:285-292: the term planes of a kForcedTerms
+  /// fitter (NTerms() - 1 full-image planes, rows of `width` floats). The
+  /// single algorithm takes them as they are; in gridded runs every
+  /// subimage's algorithm gets the same full planes with its own origin
+  /// (where the reference trims a copy per subimage, :340-349).
+  void SetSpectrallyForcedImages(std::vector<std::vector<float>> planes, size_t width);
   /// Auto-masking (parallel_deconvolution.cc:260-268): passed to the
   /// multiscale algorithms; gridded runs keep full-image per-scale masks and
   /// hand each subimage its box (:359-390), merging it back inside the
@@ -85,6 +91,7 @@ class ParallelDeconvolution {
     workers_.clear();
     worker_main_device_ = -1;
     mask_ = nullptr;
+    forced_images_.reset();
   }
   /// Share the subimages of gridded runs with the other ranks of a
   /// process-per-GPU job (a size-1 communicator runs them all here, in the
@@ -159,6 +166,7 @@ class ParallelDeconvolution {
   const Settings& settings_;
   const bool* mask_ = nullptr;
   std::shared_ptr<const std::vector<float>> rms_image_;  // full image (gridded)
+  std::shared_ptr<const ForcedTermImages> forced_images_;  // full image (gridded)
   std::unique_ptr<ComponentList> component_list_;        // gridded multiscale
   size_t rms_width_ = 0;
   std::shared_ptr<Communicator> comm_;

@@ -4,9 +4,11 @@
 #include "host_profile.h"
 
 #include <cmath>
+#include <sstream>
 #include <stdexcept>
 
 #include "device.h"
+#include "fits_image.h"
 #include "generic_clean.h"
 #include "image_accessors.h"
 #include "image_set.h"
@@ -123,9 +125,10 @@ void Radler::Perform(bool& another_iteration_required,
 
   const bool auto_mask_is_enabled =
       settings_.auto_mask_sigma || settings_.absolute_auto_mask_threshold;
-  const bool local_rms = settings_.local_rms.method != LocalRmsMethod::kNone;
-  if (!settings_.local_rms.image.empty())
-    Unsupported("A local-RMS image file (FITS input)");
+  // an RMS image file takes precedence over a constructed one (:189-196)
+  const bool rms_from_file = !settings_.local_rms.image.empty();
+  const bool local_rms =
+      !rms_from_file && settings_.local_rms.method != LocalRmsMethod::kNone;
   const size_t n_px = image_width_ * image_height_;
   gpu::Buffer integrated;
   double median = 0.0, stddev = 0.0;
@@ -153,7 +156,24 @@ void Radler::Perform(bool& another_iteration_required,
           settings_.component_optimization_algorithm);
   } else {
     parallel_deconvolution_->SetMinorLoopGain(settings_.minor_loop_gain);
-    if (local_rms) {  // :196-216
+    if (rms_from_file) {  // :189-195
+      if (rms_file_image_.empty()) {
+        FitsImageReader reader(settings_.local_rms.image, "Local RMS image file");
+        if (reader.Width() != image_width_ || reader.Height() != image_height_)
+          throw std::runtime_error(
+              "The local RMS image '" + settings_.local_rms.image +
+              "' does not have the dimensions of the deconvolved image");
+        rms_file_image_.resize(n_px);
+        reader.ReadIndex(rms_file_image_.data(), 0);
+      }
+      gpu::Buffer rms(s, n_px * sizeof(float));
+      s.H2D(rms.Ptr(), rms_file_image_.data(), n_px * sizeof(float));
+      stddev = math::rms_image::MakeRmsFactorImage(s, rms.F(), n_px,
+                                                   settings_.local_rms.strength);
+      auto factor = std::make_shared<std::vector<float>>(n_px);
+      s.D2H(factor->data(), rms.F(), n_px * sizeof(float));
+      parallel_deconvolution_->SetRmsFactorImage(std::move(factor), image_width_);
+    } else if (local_rms) {  // :196-216
       gpu::Buffer rms(s, n_px * sizeof(float));
       if (settings_.local_rms.method == LocalRmsMethod::kRmsWindow)
         math::rms_image::Make(s, rms.F(), integrated.F(), image_width_, image_height_,
@@ -253,8 +273,8 @@ void Radler::Perform(bool& another_iteration_required,
   residual_set.AssignAndStoreResidual();
   const algorithms::DeconvolutionAlgorithm& first =
       parallel_deconvolution_->FirstAlgorithm();
-  model_set.InterpolateAndStoreModel(first.HasSpectralFitter() ? &first.Fitter()
-                                                               : nullptr);
+  model_set.InterpolateAndStoreModel(first.HasSpectralFitter() ? &first.Fitter() : nullptr,
+                                     first.SpectrallyForcedImages().get());
 }
 
 std::unique_ptr<schaapcommon::fitters::SpectralFitter>
@@ -279,12 +299,7 @@ void Radler::InitializeDeconvolutionAlgorithm(
     log::Warn() << "No proper beam size available in deconvolution!\n";
     beam_size_ = 0.0;
   }
-  if (settings_.spectral_fitting.mode ==
-      schaapcommon::fitters::SpectralFittingMode::kForcedTerms)
-    Unsupported("Forced-term spectral fitting (a FITS spectral-term cube)");
-  if (!settings_.fits_mask.empty() || !settings_.casa_mask.empty() ||
-      settings_.horizon_mask_distance)
-    Unsupported("Mask files / horizon masks");
+  if (!settings_.casa_mask.empty()) Unsupported("A CASA mask (casacore table input)");
   std::unique_ptr<algorithms::DeconvolutionAlgorithm> algorithm;
   switch (settings_.algorithm_type) {
     case AlgorithmType::kGenericClean:
@@ -317,6 +332,98 @@ void Radler::InitializeDeconvolutionAlgorithm(
   algorithm->SetSpectralFitter(CreateSpectralFitter(),
                                table_->OriginalGroups().front().size());
   parallel_deconvolution_->SetAlgorithm(std::move(algorithm));
+  if (settings_.spectral_fitting.mode ==
+      schaapcommon::fitters::SpectralFittingMode::kForcedTerms)
+    ReadForcedSpectrumImages();
+  ReadMask(*table_);
+}
+
+void Radler::ReadForcedSpectrumImages() {  // :410-432
+  if (settings_.component_optimization_algorithm != OptimizationAlgorithm::kClean)
+    throw std::runtime_error(
+        "Component optimization cannot be combined with forced-term spectral fitting");
+  log::Debug() << "Reading " << settings_.spectral_fitting.forced_filename << ".\n";
+  FitsImageReader reader(settings_.spectral_fitting.forced_filename, "Forced spectrum file");
+  if (reader.Width() != image_width_ || reader.Height() != image_height_)
+    throw std::runtime_error(
+        "The image dimensions of the forced spectrum fits file do not match "
+        "the deconvolved image dimensions");
+  if (reader.NImages() + 1 != settings_.spectral_fitting.terms)
+    throw std::runtime_error(
+        "The number of images in the forced spectrum fits file does not match "
+        "the deconvolved image dimensions");
+  std::vector<std::vector<float>> terms(reader.NImages());
+  for (size_t t = 0; t != terms.size(); ++t) {
+    terms[t].resize(image_width_ * image_height_);
+    reader.ReadIndex(terms[t].data(), t);
+  }
+  parallel_deconvolution_->SetSpectrallyForcedImages(std::move(terms), image_width_);
+}
+
+void Radler::ReadMask(const WorkTable& group_table) {  // :434-527
+  const size_t n_px = image_width_ * image_height_;
+  bool has_mask = false;
+  if (!settings_.fits_mask.empty()) {
+    FitsImageReader mask_reader(settings_.fits_mask, "Fits mask file");
+    if (mask_reader.Width() != image_width_ || mask_reader.Height() != image_height_)
+      throw std::runtime_error(
+          "Specified Fits file mask did not have same dimensions as output "
+          "image!");
+    std::vector<float> mask_data(n_px);
+    if (mask_reader.NFrequencies() == 1) {
+      log::Debug() << "Reading mask '" << settings_.fits_mask << "'...\n";
+      mask_reader.ReadIndex(mask_data.data(), 0);
+    } else if (mask_reader.NFrequencies() == settings_.channels_out) {
+      const size_t index = group_table.Front().mask_channel_index;
+      log::Debug() << "Reading mask '" << settings_.fits_mask << "' (" << (index + 1)
+                   << ")...\n";
+      mask_reader.ReadIndex(mask_data.data(), index);
+    } else {
+      std::stringstream msg;
+      msg << "The number of frequencies in the specified fits mask ("
+          << mask_reader.NFrequencies()
+          << ") does not match the number of requested output channels ("
+          << settings_.channels_out << ")";
+      throw std::runtime_error(msg.str());
+    }
+    clean_mask_.assign(n_px, 0);
+    for (size_t i = 0; i != n_px; ++i) clean_mask_[i] = mask_data[i] != 0.0f ? 1 : 0;
+    has_mask = true;
+  }
+
+  if (settings_.horizon_mask_distance) {  // :484-524
+    if (!has_mask) {
+      clean_mask_.assign(n_px, 1);
+      has_mask = true;
+    }
+    double fov_sq = M_PI_2 - *settings_.horizon_mask_distance;
+    if (fov_sq < 0.0) fov_sq = 0.0;
+    if (fov_sq <= M_PI_2) {
+      fov_sq = std::sin(fov_sq);
+    } else {  // a negative horizon distance was given
+      fov_sq = 1.0 - *settings_.horizon_mask_distance;
+    }
+    fov_sq = fov_sq * fov_sq;
+    uint8_t* ptr = clean_mask_.data();
+    for (size_t y = 0; y != image_height_; ++y) {
+      for (size_t x = 0; x != image_width_; ++x) {
+        double l, m;
+        aocommon::ImageCoordinates::XYToLM(x, y, pixel_scale_x_, pixel_scale_y_,
+                                           image_width_, image_height_, l, m);
+        if (l * l + m * m >= fov_sq) *ptr = 0;
+        ++ptr;
+      }
+    }
+    log::Info() << "Saving horizon mask...\n";
+    std::vector<float> image(n_px);
+    for (size_t i = 0; i != n_px; ++i) image[i] = clean_mask_[i] ? 1.0f : 0.0f;
+    std::string filename = settings_.horizon_mask_filename;
+    if (filename.empty()) filename = settings_.prefix_name + "-horizon-mask.fits";
+    WriteFitsImage(filename, image.data(), image_width_, image_height_,
+                   settings_.pixel_scale.x, settings_.pixel_scale.y);
+  }
+  if (has_mask)
+    parallel_deconvolution_->SetCleanMask(reinterpret_cast<const bool*>(clean_mask_.data()));
 }
 
 void Radler::FreeDeconvolutionAlgorithms() {

@@ -60,6 +60,10 @@ class Radler {
  private:
   Radler(const Settings& settings, double beam_size);
   void InitializeDeconvolutionAlgorithm(std::unique_ptr<WorkTable> table);
+  /// radler.cc:410-432: the term cube of settings.spectral_fitting.forced_filename
+  void ReadForcedSpectrumImages();
+  /// radler.cc:434-527: settings.fits_mask and the horizon mask
+  void ReadMask(const WorkTable& group_table);
 
   const Settings settings_;
   std::unique_ptr<WorkTable> table_;
@@ -74,6 +78,8 @@ class Radler {
   bool auto_mask_is_finished_ = false;
   size_t auto_mask_finishing_iteration_ = 0;
   std::vector<uint8_t> auto_mask_;  // scale-independent mask (non-multiscale)
+  std::vector<uint8_t> clean_mask_;  // fits / horizon mask (bool as bytes)
+  std::vector<float> rms_file_image_;  // settings.local_rms.image, read once
 };
 
 }  // namespace radler

@@ -164,8 +164,27 @@ std::vector<float> ComponentFitMatrix(
   return g;
 }
 
+namespace {
+void FillLogPoly(const schaapcommon::fitters::SpectralFitter& f, rdl_logpoly* out);
+}
+
 bool MakeLogPoly(const schaapcommon::fitters::SpectralFitter& f, rdl_logpoly* out) {
   if (f.Mode() != schaapcommon::fitters::SpectralFittingMode::kLogPolynomial) return false;
+  FillLogPoly(f, out);
+  return true;
+}
+
+bool MakeForcedLogPoly(const schaapcommon::fitters::SpectralFitter& f, rdl_logpoly* out,
+                       float* weights) {
+  if (f.Mode() != schaapcommon::fitters::SpectralFittingMode::kForcedTerms) return false;
+  FillLogPoly(f, out);
+  for (size_t c = 0; c != RDL_LOGPOLY_MAX_CHANNELS; ++c)
+    weights[c] = c < f.Weights().size() ? f.Weights()[c] : 0.0f;
+  return true;
+}
+
+namespace {
+void FillLogPoly(const schaapcommon::fitters::SpectralFitter& f, rdl_logpoly* out) {
   const std::vector<double>& freqs = f.Frequencies();
   const std::vector<float>& weights = f.Weights();
   if (freqs.empty() || freqs.size() > RDL_LOGPOLY_MAX_CHANNELS)
@@ -182,8 +201,8 @@ bool MakeLogPoly(const schaapcommon::fitters::SpectralFitter& f, rdl_logpoly* ou
     lp.lg[c] = std::log10(freqs[c] / f.ReferenceFrequency());
   }
   *out = lp;
-  return true;
 }
+}  // namespace
 
 }  // namespace radler
 
@@ -214,10 +233,39 @@ SpectralFitter::SpectralFitter(SpectralFittingMode mode, size_t n_terms,
              "convergence criteria are assumptions).\n";
     });
   }
+  if (mode_ == SpectralFittingMode::kForcedTerms) {
+    // schaapcommon's forced-term fit is not vendored with the reference
+    // either: the restated estimate (csrc/hip/logpoly.h) is unpinned
+    static std::once_flag warned;
+    std::call_once(warned, [] {
+      radler::log::Warn()
+          << "Warning: forced-term spectral fitting uses a restated "
+             "weighted-mean flux estimate; its parity with schaapcommon's "
+             "forced-term fitter is unverified (term convention and the "
+             "estimator are assumptions).\n";
+    });
+  }
 }
 
-void SpectralFitter::Fit(std::vector<float>& terms, const float* values, size_t,
-                         size_t) const {
+void SpectralFitter::SetForcedTerms(std::vector<std::vector<float>> planes, size_t width) {
+  if (mode_ != SpectralFittingMode::kForcedTerms)
+    throw std::runtime_error("SetForcedTerms: the fitter is not in forced-terms mode");
+  if (n_terms_ == 0 || planes.size() + 1 != n_terms_)
+    throw std::runtime_error("SetForcedTerms: " + std::to_string(planes.size()) +
+                             " term planes given, a fit of " + std::to_string(n_terms_) +
+                             " terms needs " +
+                             std::to_string(n_terms_ == 0 ? 0 : n_terms_ - 1));
+  for (const std::vector<float>& p : planes)
+    if (width == 0 || p.empty() || p.size() != planes.front().size() || p.size() % width != 0)
+      throw std::runtime_error(
+          "SetForcedTerms: the term planes must be non-empty, of equal size and made of "
+          "rows of the given width");
+  forced_planes_ = std::move(planes);
+  forced_width_ = width;
+}
+
+void SpectralFitter::Fit(std::vector<float>& terms, const float* values, size_t x,
+                         size_t y) const {
   switch (mode_) {
     case SpectralFittingMode::kNoFitting:
       return;
@@ -240,17 +288,33 @@ void SpectralFitter::Fit(std::vector<float>& terms, const float* values, size_t,
       rdl::lp::Fit(lp, values, terms.data());
       return;
     }
-    case SpectralFittingMode::kForcedTerms:
-      break;
+    case SpectralFittingMode::kForcedTerms: {
+      if (n_terms_ > 1 && forced_planes_.empty())
+        throw std::runtime_error(
+            "SpectralFitter: forced-term fitting needs term planes (SetForcedTerms)");
+      rdl_logpoly lp;
+      float weights[RDL_LOGPOLY_MAX_CHANNELS];
+      radler::MakeForcedLogPoly(*this, &lp, weights);
+      terms.assign(n_terms_, 0.0f);
+      if (n_terms_ > 1) {
+        const size_t height = forced_planes_.front().size() / forced_width_;
+        if (x >= forced_width_ || y >= height)
+          throw std::runtime_error("SpectralFitter: pixel outside the forced-term planes");
+        for (size_t k = 1; k != n_terms_; ++k)
+          terms[k] = forced_planes_[k - 1][y * forced_width_ + x];
+      }
+      double shape[RDL_LOGPOLY_MAX_CHANNELS];
+      terms[0] = rdl::lp::ForcedFit(lp, weights, terms.data(), values, shape);
+      return;
+    }
   }
-  throw std::runtime_error(
-      "SpectralFitter: forced-term fitting is not available in the MI355X build");
 }
 
 float SpectralFitter::Evaluate(const std::vector<float>& terms,
                                double frequency) const {
   if (terms.empty()) return 0.0f;
-  if (mode_ == SpectralFittingMode::kLogPolynomial)
+  if (mode_ == SpectralFittingMode::kLogPolynomial ||
+      mode_ == SpectralFittingMode::kForcedTerms)
     return rdl::lp::Evaluate(terms.data(), int(terms.size()),
                              std::log10(frequency / reference_frequency_));
   const float x = float(frequency / reference_frequency_ - 1.0);

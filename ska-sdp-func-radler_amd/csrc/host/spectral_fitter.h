@@ -12,8 +12,10 @@
 //                  a non-linear least-squares fit over the same channels
 //                  (csrc/hip/logpoly.h states it; the same code runs in the
 //                  device loops, so host and device fits agree).
-// kForcedTerms (terms read from a FITS cube) stays unavailable: Radler
-// rejects it with an error.
+//   kForcedTerms   the same S, but t1, t2, ... of a component are read from
+//                  term planes at its pixel (x, y) and only t0 is fitted: the
+//                  weighted mean of the values over that of the shape
+//                  (csrc/hip/logpoly.h states it, host and device share it).
 //
 // Fitting then evaluating a polynomial at fixed frequencies and weights is a
 // linear map of the channel values, independent of the pixel. SpectralMaps
@@ -56,6 +58,13 @@ class SpectralFitter {
   void FitAndEvaluate(float* values, size_t x, size_t y,
                       std::vector<float>& scratch) const;
 
+  /// kForcedTerms: NTerms() - 1 planes of equal size (rows of `width`
+  /// floats); plane k holds term k + 1 of every pixel. Throws when the plane
+  /// count or a size does not fit.
+  void SetForcedTerms(std::vector<std::vector<float>> planes, size_t width);
+  const std::vector<std::vector<float>>& ForcedPlanes() const { return forced_planes_; }
+  size_t ForcedWidth() const { return forced_width_; }
+
  private:
   SpectralFittingMode mode_;
   size_t n_terms_;
@@ -64,12 +73,23 @@ class SpectralFitter {
   double reference_frequency_ = 0.0;
   // kPolynomial: terms = fit_ * values (n_terms_ x n_channels, row-major)
   std::vector<double> fit_;
+  // kForcedTerms: terms 1.. per pixel
+  std::vector<std::vector<float>> forced_planes_;
+  size_t forced_width_ = 0;
 };
 
 }  // namespace schaapcommon::fitters
 #endif  // RADLER_AMD_USE_EXTERNAL_AOCOMMON
 
 namespace radler {
+
+/// Forced spectral-term planes of the full image (kForcedTerms): plane k
+/// holds term k + 1 of every pixel, rows of `width` floats. Shared by the
+/// algorithms of a grid's subimages.
+struct ForcedTermImages {
+  std::vector<float> data;  // n_planes x height x width
+  size_t n_planes = 0, width = 0, height = 0;
+};
 
 /// The linear maps of a polynomial fitter (empty when the fitter needs none:
 /// kNoFitting, or no channel frequencies).
@@ -108,5 +128,11 @@ std::vector<float> ComponentFitMatrix(
 /// The device description of a kLogPolynomial fitter (false for the other
 /// modes); throws when the channel or term count exceeds the device limits.
 bool MakeLogPoly(const schaapcommon::fitters::SpectralFitter& f, rdl_logpoly* out);
+
+/// The same description (channels, lg, n_terms) of a kForcedTerms fitter, and
+/// its channel weights (RDL_LOGPOLY_MAX_CHANNELS floats); false for the other
+/// modes.
+bool MakeForcedLogPoly(const schaapcommon::fitters::SpectralFitter& f, rdl_logpoly* out,
+                       float* weights);
 
 }  // namespace radler

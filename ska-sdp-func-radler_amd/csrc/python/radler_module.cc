@@ -12,6 +12,7 @@
 #include "communicator.h"
 #include "device.h"
 #include "device_run.h"
+#include "fits_image.h"
 #include "dijkstra_splitter.h"
 #include "image_accessors.h"
 #include "logger.h"
@@ -202,7 +203,60 @@ void InitSpectralFitter(py::module& m) {
       .def("evaluate",
            [](const SpectralFitter& self, const std::vector<float>& terms,
               double frequency) { return self.Evaluate(terms, frequency); },
-           py::arg("terms"), py::arg("frequency"));
+           py::arg("terms"), py::arg("frequency"))
+      .def("set_forced_terms",
+           [](SpectralFitter& self, const std::vector<FloatArray>& planes) {
+             // forced_terms mode: n_terms - 1 planes (height, width); fit(values,
+             // x, y) then takes the terms after the first from pixel (x, y)
+             std::vector<std::vector<float>> data;
+             size_t width = 0;
+             for (const FloatArray& p : planes) {
+               if (p.ndim() != 2)
+                 throw std::runtime_error("set_forced_terms: 2-D arrays are required");
+               if (!data.empty() && size_t(p.shape(1)) != width)
+                 throw std::runtime_error("set_forced_terms: the planes differ in width");
+               width = size_t(p.shape(1));
+               data.emplace_back(p.data(), p.data() + p.size());
+             }
+             self.SetForcedTerms(std::move(data), width);
+           },
+           py::arg("planes"));
+}
+
+void InitIo(py::module& m) {
+  // csrc/host/fits_image.h: the FITS images Radler reads (term cubes, masks,
+  // RMS images) and writes (the horizon mask)
+  py::module io = m.def_submodule("io", "Minimal FITS image reader / writer");
+  io.def(
+      "read_fits",
+      [](const std::string& path) {
+        // (planes [n_images][height][width], n_images, n_frequencies)
+        radler::FitsImageReader reader(path);
+        py::array_t<float> planes({py::ssize_t(reader.NImages()),
+                                   py::ssize_t(reader.Height()),
+                                   py::ssize_t(reader.Width())});
+        reader.Read(planes.mutable_data());
+        return py::make_tuple(planes, reader.NImages(), reader.NFrequencies());
+      },
+      py::arg("path"));
+  io.def(
+      "read_fits_index",
+      [](const std::string& path, size_t index) {
+        radler::FitsImageReader reader(path);
+        py::array_t<float> plane({py::ssize_t(reader.Height()), py::ssize_t(reader.Width())});
+        reader.ReadIndex(plane.mutable_data(), index);
+        return plane;
+      },
+      py::arg("path"), py::arg("index"));
+  io.def(
+      "write_fits",
+      [](const std::string& path, FloatArray image, double pixel_scale_x,
+         double pixel_scale_y) {
+        if (image.ndim() != 2) throw std::runtime_error("write_fits: a 2-D image is required");
+        radler::WriteFitsImage(path, image.data(), size_t(image.shape(1)),
+                               size_t(image.shape(0)), pixel_scale_x, pixel_scale_y);
+      },
+      py::arg("path"), py::arg("image"), py::arg("pixel_scale_x"), py::arg("pixel_scale_y"));
 }
 
 void InitWorkTable(py::module& m) {  // python/pywork_table.cc
@@ -993,6 +1047,7 @@ PYBIND11_MODULE(radler, m) {  // python/pywrappers.cc
   InitSettings(m);
   InitWorkTable(m);
   InitSpectralFitter(m);
+  InitIo(m);
   InitRadler(m);
   InitComponentList(m);
   InitGpu(m);
