@@ -832,6 +832,33 @@ int rdl_comm_broadcast(rdl_session* s, void* d_buf, size_t bytes, int root);
 /* This session's rank and the communicator size. */
 int rdl_comm_rank(rdl_session* s, int* rank, int* n_ranks);
 
+/* ------------------------------------- major-iteration passes (appended) */
+/* rdl_conv_convolve_subtract with the peak search of the corrected residual
+ * (rdl_find_peak_enqueue(d_residual, img_w, img_h, 0, img_h, h_border,
+ * v_border, allow_negative, d_mask, avx_semantics, slot): same box, mask and
+ * sign rules, same result in peak slot `slot`) fused into the inverse row
+ * pass, over the values as written: the residual is not read again. Only the
+ * plans with compile-time rows (rdl_conv_fast(c) & RDL_CONV_FAST_ROWS) have
+ * the fused form. On any other plan the correction runs as
+ * rdl_conv_convolve_subtract does, nothing is queued for the peak (the slot
+ * keeps its content) and the call returns RDL_NOT_FUSED, which is not an
+ * error. */
+#define RDL_NOT_FUSED 6
+int rdl_conv_convolve_subtract_peak(rdl_conv* c, const float* d_image, uint32_t img_w,
+                                    uint32_t img_h, uint32_t ox, uint32_t oy,
+                                    const void* d_kernel, int kernel_layout, int kernel_f32,
+                                    double scale, const uint8_t* d_row_mask, void* d_work,
+                                    float* d_residual, uint32_t h_border, uint32_t v_border,
+                                    int allow_negative, const uint8_t* d_mask,
+                                    int avx_semantics, uint32_t slot);
+/* Bitwise comparison of two device buffers of `bytes` bytes (a multiple of
+ * 4), stream ordered: sets the session's difference flag when any word
+ * differs. `first` != 0 clears the flag before comparing, so a chain of
+ * calls accumulates; rdl_bits_differ_collect waits and reads the flag. */
+int rdl_bits_differ_enqueue(rdl_session* s, const void* d_a, const void* d_b, size_t bytes,
+                            int first);
+int rdl_bits_differ_collect(rdl_session* s, int* differ);
+
 #ifdef __cplusplus
 }
 #endif

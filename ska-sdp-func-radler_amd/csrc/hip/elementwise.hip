@@ -89,6 +89,31 @@ __global__ void AddShapeKernel(float* image, uint32_t width, const float* k,
   px = __builtin_fmaf(kv, gain, px);
 }
 
+// word-wise comparison of two buffers (the PSF cache's content check): any
+// differing word sets *flag (every writer stores the same value)
+__global__ __launch_bounds__(256) void BitsDifferKernel(const uint32_t* __restrict__ a,
+                                                        const uint32_t* __restrict__ b,
+                                                        size_t n, uint32_t* flag) {
+  const size_t n4 = (reinterpret_cast<uintptr_t>(a) % 16 == 0 &&
+                     reinterpret_cast<uintptr_t>(b) % 16 == 0)
+                        ? n / 4
+                        : 0;
+  const uint4* a4 = reinterpret_cast<const uint4*>(a);
+  const uint4* b4 = reinterpret_cast<const uint4*>(b);
+  bool differ = false;
+  for (size_t i = blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n4;
+       i += size_t(gridDim.x) * blockDim.x) {
+    const uint4 x = a4[i], y = b4[i];
+    differ = differ || x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w;
+  }
+  for (size_t i = n4 * 4 + blockIdx.x * size_t(blockDim.x) + threadIdx.x; i < n;
+       i += size_t(gridDim.x) * blockDim.x)
+    differ = differ || a[i] != b[i];
+  if (differ) *flag = 1u;
+}
+
+__global__ void ClearFlagKernel(uint32_t* flag) { *flag = 0u; }
+
 inline unsigned GridFor(size_t n) {
   return unsigned(std::min<size_t>(8192, std::max<size_t>(1, DivUp(n, 256))));
 }
@@ -230,6 +255,31 @@ int rdl_complex_narrow(rdl_session* s, void* d_dst, const void* d_src, size_t n_
                              s->stream>>>(static_cast<float2*>(d_dst),
                                           static_cast<const double2*>(d_src), n_complex);
   RDL_HIP_CHECK(hipGetLastError());
+  return RDL_OK;
+}
+
+int rdl_bits_differ_enqueue(rdl_session* s, const void* d_a, const void* d_b, size_t bytes,
+                            int first) {
+  RDL_ARG_CHECK(s && (bytes == 0 || (d_a && d_b)), "NULL argument");
+  RDL_ARG_CHECK(bytes % 4 == 0 && reinterpret_cast<uintptr_t>(d_a) % 4 == 0 &&
+                    reinterpret_cast<uintptr_t>(d_b) % 4 == 0,
+                "buffers of whole 4-byte words");
+  uint32_t* flag = static_cast<uint32_t*>(rdl::MappedResult(s, rdl::kMappedDiffer));
+  if (first) rdl::ClearFlagKernel<<<1, 1, 0, s->stream>>>(flag);
+  const size_t n = bytes / 4;
+  if (n != 0)
+    rdl::BitsDifferKernel<<<rdl::GridFor(n / 4 + 1), 256, 0, s->stream>>>(
+        static_cast<const uint32_t*>(d_a), static_cast<const uint32_t*>(d_b), n, flag);
+  RDL_HIP_CHECK(hipGetLastError());
+  return RDL_OK;
+}
+
+int rdl_bits_differ_collect(rdl_session* s, int* differ) {
+  RDL_ARG_CHECK(s && differ, "NULL argument");
+  uint32_t v = 0;
+  const rdl::SmallRead r{&v, rdl::MappedResult(s, rdl::kMappedDiffer), sizeof(v)};
+  RDL_TRY(rdl::ReadSmall(s, &r, 1));
+  *differ = v != 0;
   return RDL_OK;
 }
 

@@ -1090,11 +1090,13 @@ size_t rdl_conv_convolve_subtract_bytes(const rdl_conv* c) {
                     : size_t(SpectrumBytes(c));
 }
 
-int rdl_conv_convolve_subtract(rdl_conv* c, const float* d_image, uint32_t img_w,
-                               uint32_t img_h, uint32_t ox, uint32_t oy,
-                               const void* d_kernel, int kernel_layout, int kernel_f32,
-                               double scale, const uint8_t* d_row_mask, void* d_work,
-                               float* d_residual) {
+namespace {
+// rdl_conv_convolve_subtract; `peak` (plans with compile-time rows only): the
+// fused search of the inverse row pass, one partial per image row
+int ConvolveSubtract(rdl_conv* c, const float* d_image, uint32_t img_w, uint32_t img_h,
+                     uint32_t ox, uint32_t oy, const void* d_kernel, int kernel_layout,
+                     int kernel_f32, double scale, const uint8_t* d_row_mask, void* d_work,
+                     float* d_residual, const rdl::RowPeak* peak) {
   RDL_ARG_CHECK(c && d_image && d_kernel && d_work && d_residual, "NULL argument");
   RDL_ARG_CHECK(uint64_t(ox) + img_w <= c->width && uint64_t(oy) + img_h <= c->height,
                 "image window outside the plane");
@@ -1105,7 +1107,13 @@ int rdl_conv_convolve_subtract(rdl_conv* c, const float* d_image, uint32_t img_w
                 : rdl_conv_rows_forward(c, d_image, img_w, img_h, ox, oy, d_work));
     RDL_TRY(rdl_conv_columns_window(c, d_work, d_work, d_kernel, scale, d_row_mask,
                                     kernel_layout, oy, img_h, kernel_f32));
-    return rdl_conv_rows_inverse(c, d_work, d_residual, img_w, img_h, ox, oy, 1);
+    if (!peak) return rdl_conv_rows_inverse(c, d_work, d_residual, img_w, img_h, ox, oy, 1);
+    // rdl_conv_rows_inverse's launch on these plans, with the search
+    rdl::ScopedTiming t(c->s, c->f64 ? "conv64_rows" : "conv_rows",
+                        SpectrumBytes(c) + double(img_w) * img_h * 8.0);
+    return rdl::FastRowsInverseLaunch(c->s, c->fast_rows, d_work, d_residual, c->tw_row,
+                                      c->ptw_row, c->height, img_w, img_h, ox, oy, 1,
+                                      c->tiled ? 1 : 0, peak, c->twd_row);
   }
   RDL_ARG_CHECK(kernel_layout == RDL_CONV_ROW_MAJOR || kernel_layout == RDL_CONV_COL_MAJOR,
                 "bad kernel layout");
@@ -1141,8 +1149,60 @@ int rdl_conv_convolve_subtract(rdl_conv* c, const float* d_image, uint32_t img_w
   }
   rdl::ScopedTiming t(c->s, "conv64_rows", win + double(img_w) * img_h * 8.0);
   return rdl::FastRowsInverseLaunch(c->s, c->fast_rows, d_work, d_residual, c->tw_row,
-                                    c->ptw_row, c->height, img_w, img_h, ox, oy, 1, 1, nullptr,
+                                    c->ptw_row, c->height, img_w, img_h, ox, oy, 1, 1, peak,
                                     c->twd_row);
+}
+}  // namespace
+
+int rdl_conv_convolve_subtract(rdl_conv* c, const float* d_image, uint32_t img_w,
+                               uint32_t img_h, uint32_t ox, uint32_t oy,
+                               const void* d_kernel, int kernel_layout, int kernel_f32,
+                               double scale, const uint8_t* d_row_mask, void* d_work,
+                               float* d_residual) {
+  return ConvolveSubtract(c, d_image, img_w, img_h, ox, oy, d_kernel, kernel_layout,
+                          kernel_f32, scale, d_row_mask, d_work, d_residual, nullptr);
+}
+
+int rdl_conv_convolve_subtract_peak(rdl_conv* c, const float* d_image, uint32_t img_w,
+                                    uint32_t img_h, uint32_t ox, uint32_t oy,
+                                    const void* d_kernel, int kernel_layout, int kernel_f32,
+                                    double scale, const uint8_t* d_row_mask, void* d_work,
+                                    float* d_residual, uint32_t h_border, uint32_t v_border,
+                                    int allow_negative, const uint8_t* d_mask,
+                                    int avx_semantics, uint32_t slot) {
+  RDL_ARG_CHECK(c, "NULL argument");
+  RDL_ARG_CHECK(slot < RDL_PEAK_SLOTS, "peak slot out of range");
+  RDL_ARG_CHECK(img_w > 0 && img_h > 0, "empty image");
+  RDL_ARG_CHECK(uint64_t(img_w) * img_h < 0xffffffffull,
+                "image too large for 32-bit pixel index");
+  if (!c->fast_rows) {  // the runtime-plan row kernels have no search
+    RDL_TRY(ConvolveSubtract(c, d_image, img_w, img_h, ox, oy, d_kernel, kernel_layout,
+                             kernel_f32, scale, d_row_mask, d_work, d_residual, nullptr));
+    return RDL_NOT_FUSED;
+  }
+  rdl_session* s = c->s;
+  // the box of LaunchFindPeak(start_y 0, end_y img_h) (peak_finder.cc:27-32,
+  // unsigned wrap-around as there); an empty box has xe == xs or ye == ys
+  rdl::RowPeak pk{};
+  pk.xs = h_border;
+  pk.xe = img_w - h_border;
+  pk.ys = v_border;
+  pk.ye = img_h < img_h - v_border ? img_h : img_h - v_border;
+  if (pk.xe < pk.xs) pk.xe = pk.xs;
+  if (pk.ye < pk.ys) pk.ye = pk.ys;
+  if (pk.xe > img_w) pk.xe = img_w;
+  if (pk.ye > img_h) pk.ye = img_h;
+  if (pk.xe < pk.xs) pk.xe = pk.xs;  // a border wider than the image
+  if (pk.ye < pk.ys) pk.ye = pk.ys;
+  pk.mask = d_mask;
+  pk.allow_negative = allow_negative;
+  // the slot's partials area, as rdl_conv_rows_inverse_peak lays them out
+  RDL_TRY(s->EnsureScratch(s->partials, RDL_PEAK_SLOTS * size_t(img_h) * sizeof(uint64_t)));
+  pk.partials = static_cast<uint64_t*>(s->partials.ptr) + size_t(slot) * img_h;
+  RDL_TRY(ConvolveSubtract(c, d_image, img_w, img_h, ox, oy, d_kernel, kernel_layout,
+                           kernel_f32, scale, d_row_mask, d_work, d_residual, &pk));
+  return rdl::LaunchPeakFinal(s, pk.partials, img_h, d_residual, img_w, img_h, avx_semantics,
+                              d_mask != nullptr, rdl::PeakSlot(s, slot));
 }
 
 int rdl_conv_columns_layout(rdl_conv* c, const void* d_in, void* d_out,

@@ -516,6 +516,7 @@ inline void* MappedResult(rdl_session* s, size_t offset) {
 constexpr size_t kMappedSelTotal = 0;      // uint64_t selection count
 constexpr size_t kMappedPeak = 64;         // PeakOut of rdl_find_peak
 constexpr size_t kMappedRms = 128;         // float of rdl_rms
+constexpr size_t kMappedDiffer = 192;      // uint32_t flag of rdl_bits_differ_*
 constexpr size_t kMappedLoop = 4096;       // sub-minor LoopResult (+ phase probes)
 constexpr size_t kMappedPeakSlots = 32 * 1024;
 // the device small buffer's last 1 KiB: peak search tickets (PeakTicket),

@@ -261,19 +261,31 @@ void Fft::ForwardColumnMajor(const float* d_in, void* d_spectrum) {
         "rdl_conv_columns_ex");
 }
 
-void Fft::ConvolveSubtract(const float* d_image, size_t img_w, size_t img_h,
+bool Fft::ConvolveSubtract(const float* d_image, size_t img_w, size_t img_h,
                            size_t ox, size_t oy, const void* d_kernel_spectrum,
                            void* d_work, float* d_residual,
                            const uint8_t* d_row_mask, bool kernel_col_major,
-                           bool kernel_f32) {
+                           bool kernel_f32, const PeakRequest* peak) {
   if (!conv_) throw std::logic_error("Fft::ConvolveSubtract needs the LDS engine");
   const double norm = 1.0 / (double(width_) * double(height_));
+  if (peak) {
+    const int rc = rdl_conv_convolve_subtract_peak(
+        conv_, d_image, uint32_t(img_w), uint32_t(img_h), uint32_t(ox), uint32_t(oy),
+        d_kernel_spectrum, kernel_col_major ? RDL_CONV_COL_MAJOR : RDL_CONV_ROW_MAJOR,
+        kernel_f32 ? 1 : 0, f64_ ? norm : double(float(norm)), d_row_mask, d_work, d_residual,
+        peak->h_border, peak->v_border, peak->allow_negative ? 1 : 0, peak->d_mask, 1,
+        peak->slot);
+    if (rc == RDL_NOT_FUSED) return false;
+    Check(rc, "rdl_conv_convolve_subtract_peak");
+    return true;
+  }
   Check(rdl_conv_convolve_subtract(
             conv_, d_image, uint32_t(img_w), uint32_t(img_h), uint32_t(ox), uint32_t(oy),
             d_kernel_spectrum, kernel_col_major ? RDL_CONV_COL_MAJOR : RDL_CONV_ROW_MAJOR,
             kernel_f32 ? 1 : 0, f64_ ? norm : double(float(norm)), d_row_mask, d_work,
             d_residual),
         "rdl_conv_convolve_subtract");
+  return false;
 }
 
 size_t Fft::ConvolveSubtractBytes() const {

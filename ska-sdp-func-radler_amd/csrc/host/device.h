@@ -20,6 +20,15 @@ void Check(int rc, const char* what);
 
 class Session;
 
+/// A peak search (rdl_find_peak_enqueue's box, mask and sign rules, AVX
+/// semantics) whose result goes to peak slot `slot`.
+struct PeakRequest {
+  uint32_t h_border = 0, v_border = 0;
+  bool allow_negative = true;
+  const uint8_t* d_mask = nullptr;
+  uint32_t slot = 0;
+};
+
 /// A device allocation owned by one session.
 class Buffer {
  public:
@@ -92,11 +101,15 @@ class Fft {
   /// rows; kernel_col_major reads a spectrum made by ForwardColumnMajor.
   /// d_work holds ConvolveSubtractBytes() (the float64 convolution-column
   /// plans keep its spectrum in the tiled layout: rdl_conv_convolve_subtract).
-  void ConvolveSubtract(const float* d_image, size_t img_w, size_t img_h,
+  /// With `peak`: the search of the corrected residual fused into the last
+  /// pass (rdl_conv_convolve_subtract_peak); returns whether it was queued
+  /// (false: the plan has no fused form, the correction ran without it).
+  bool ConvolveSubtract(const float* d_image, size_t img_w, size_t img_h,
                         size_t ox, size_t oy, const void* d_kernel_spectrum,
                         void* d_work, float* d_residual,
                         const uint8_t* d_row_mask = nullptr,
-                        bool kernel_col_major = false, bool kernel_f32 = false);
+                        bool kernel_col_major = false, bool kernel_f32 = false,
+                        const PeakRequest* peak = nullptr);
   size_t ConvolveSubtractBytes() const;
   /// LDS engine only: forward spectrum stored column by column (column k at
   /// k * height), the layout the column pass reads contiguously.

@@ -48,6 +48,36 @@ bool FusedScalesOn() {
   return !(e && e[0] == '0');
 }
 
+// The next three are read per major iteration, like RDL_SCALE_LANES.
+// RDL_CORR_PEAK=0: the scale-0 peak search reads the corrected residual
+// again instead of running inside the correction's inverse row pass
+bool CorrPeakOn() {
+  const char* e = std::getenv("RDL_CORR_PEAK");
+  return !(e && e[0] == '0');
+}
+
+// RDL_PSF_CACHE=0: the scale-convolved PSFs and the padded PSF spectra are
+// made again in every major iteration; RDL_PSF_CACHE_MB: what the kept ones
+// may hold (default 16384; what does not fit is made again as without)
+bool PsfCacheOn() {
+  const char* e = std::getenv("RDL_PSF_CACHE");
+  return !(e && e[0] == '0');
+}
+
+size_t PsfCacheBudget() {
+  const char* e = std::getenv("RDL_PSF_CACHE_MB");
+  char* end = nullptr;
+  const unsigned long long mb = e ? std::strtoull(e, &end, 10) : 16384ull;
+  return size_t(e && end == e ? 16384ull : mb) << 20;
+}
+
+// RDL_MODEL_GATE=0: the scale > 0 model update chooses between stamping and
+// the FFT by the loop's selected pixels instead of its components
+bool ModelGateOn() {
+  const char* e = std::getenv("RDL_MODEL_GATE");
+  return !(e && e[0] == '0');
+}
+
 // joins the session's second lane if a scope exits while it is selected
 struct LaneJoin {
   rdl_session* s;
@@ -255,6 +285,9 @@ void MultiScaleAlgorithm::FindActiveScaleConvolvedMaxima(
     image_set.GetLinearIntegrated(d_integrated);
   bool need_fft = false;
   const bool fused_search = !report_rms && !RmsFactorImage();
+  // the scale-0 search the residual correction already queued in slot 0
+  const bool scale0_queued = scale0_search_queued_;
+  scale0_search_queued_ = false;
   // the scale-0 search: queued with the other scales' (one read-back for
   // all) when the convolved scales' searches are queued too
   int direct = -1;
@@ -274,7 +307,17 @@ void MultiScaleAlgorithm::FindActiveScaleConvolvedMaxima(
     }
   }
   if (!need_fft) {
-    if (direct >= 0) FindPeakDirect(d_source, size_t(direct));
+    if (direct >= 0 && scale0_queued) {
+      rdl_peak p;
+      gpu::Check(rdl_find_peak_collect(s, 1, &p), "rdl_find_peak_collect");
+      ScaleInfo& e = scale_infos_[size_t(direct)];
+      e.max_image_value_x = p.x;
+      e.max_image_value_y = p.y;
+      e.max_unnormalized_image_value = p.found ? p.value : 0.0f;
+      e.max_normalized_image_value = p.found ? Normalized(p.value, p.x, p.y, w) : 0.0f;
+    } else if (direct >= 0) {
+      FindPeakDirect(d_source, size_t(direct));
+    }
     return;
   }
   if (scale_infos_.size() + 1 > RDL_PEAK_SLOTS)
@@ -283,10 +326,11 @@ void MultiScaleAlgorithm::FindActiveScaleConvolvedMaxima(
   if (direct >= 0) {  // FindPeakDirect's search (:700-748), collected below
     const uint32_t hb = uint32_t(std::round(w * CleanBorderRatio()));
     const uint32_t vb = uint32_t(std::round(h * CleanBorderRatio()));
-    gpu::Check(rdl_find_peak_enqueue(s, d_source, uint32_t(w), uint32_t(h), 0, uint32_t(h), hb,
-                                     vb, AllowNegativeComponents(), MaskFor(size_t(direct)), 1,
-                                     0),
-               "rdl_find_peak_enqueue");
+    if (!scale0_queued)
+      gpu::Check(rdl_find_peak_enqueue(s, d_source, uint32_t(w), uint32_t(h), 0, uint32_t(h),
+                                       hb, vb, AllowNegativeComponents(),
+                                       MaskFor(size_t(direct)), 1, 0),
+                 "rdl_find_peak_enqueue");
     pending.push_back(size_t(direct));
   }
   if (fused_search && FusedScalesOn() && transforms_->Fused()) {
@@ -478,6 +522,35 @@ void MultiScaleAlgorithm::ActivateScales(size_t last) {  // :636-656
   }
 }
 
+bool MultiScaleAlgorithm::PsfCacheHit(gpu::Session& session, size_t width, size_t height,
+                                      size_t n_psf, const float* d_integrated_psf,
+                                      const gpu::Planes& psfs) {
+  const PsfCache& pc = psf_cache_;
+  if (pc.session != &session || pc.width != width || pc.height != height ||
+      pc.n_psf != n_psf || !pc.reference.buffer || pc.convolved.size() != n_psf ||
+      pc.scales.size() != scale_infos_.size() || pc.shape != settings_.shape ||
+      pc.convolution_padding != settings_.convolution_padding ||
+      pc.correction_f64 != SubMinorLoop::CorrectionF64() ||
+      pc.correction_kernel_f32 != SubMinorLoop::CorrectionKernelF32())
+    return false;
+  for (size_t si = 0; si != pc.scales.size(); ++si)
+    if (pc.scales[si] != scale_infos_[si].scale) return false;
+  // The PSFs by content: Radler::Perform loads every major iteration's PSFs
+  // into the same buffers, so their addresses say nothing.
+  prof::Section prof_check("ms.psf_cache_check");
+  rdl_session* s = session.Handle();
+  const size_t plane_bytes = width * height * sizeof(float);
+  gpu::Check(rdl_bits_differ_enqueue(s, d_integrated_psf, pc.reference.Plane(0), plane_bytes, 1),
+             "rdl_bits_differ_enqueue");
+  for (size_t i = 0; i != n_psf; ++i)
+    gpu::Check(rdl_bits_differ_enqueue(s, psfs.Plane(i), pc.reference.Plane(1 + i),
+                                       plane_bytes, 0),
+               "rdl_bits_differ_enqueue");
+  int differ = 1;
+  gpu::Check(rdl_bits_differ_collect(s, &differ), "rdl_bits_differ_collect");
+  return differ == 0;
+}
+
 DeconvolutionResult MultiScaleAlgorithm::ExecuteMajorIteration(
     ImageSet& data_image, ImageSet& model_image, const gpu::Planes& psfs) {
   prof::Section prof_section("ms.execute");
@@ -488,6 +561,7 @@ DeconvolutionResult MultiScaleAlgorithm::ExecuteMajorIteration(
   const size_t height = data_image.Height();
   const size_t npx = width * height;
   trace_.clear();
+  scale0_search_queued_ = false;
   if (StopOnNegativeComponents()) SetAllowNegativeComponents(true);
   InitializeScales(scale_infos_, beam_size_in_pixels_, std::min(width, height),
                    settings_.shape, settings_.max_scales, settings_.scale_list);
@@ -564,44 +638,95 @@ DeconvolutionResult MultiScaleAlgorithm::ExecuteMajorIteration(
       data_image.Integration(false).copy_fast_path)
     spectrum_work2_ = std::make_shared<gpu::Buffer>(session, spectrum_bytes);
 
-  // ConvolvePsfs (:29-88): convolved[psf][scale]
+  // ConvolvePsfs (:29-88): convolved[psf][scale], kept in psf_cache_ with the
+  // products made from it. A main session keeps them for the next major
+  // iteration (PsfCacheHit); otherwise they go when this call returns.
   const size_t n_psf = data_image.PsfCount();
   const size_t n_scales = scale_infos_.size();
-  std::vector<gpu::Planes> convolved(n_psf);
-  auto convolve_psfs = [&](gpu::Planes& out, const float* d_psf,
-                           bool is_integrated) {
-    out = gpu::Planes::Make(session, width, height, n_scales);
+  const size_t plane_bytes = npx * sizeof(float);
+  PsfCache& pc = psf_cache_;
+  struct CacheDrop {
+    PsfCache& c;
+    bool drop;
+    ~CacheDrop() {
+      if (drop) c = PsfCache();
+    }
+  } cache_drop{pc, !(PsfCacheOn() && !session.IsWorker())};
+  const size_t cache_budget = PsfCacheBudget();
+  // a product joins the cache while it fits the budget; what does not lives
+  // for this call in the maps beside it (below)
+  auto cache_takes = [&](size_t bytes) {
+    if (!cache_drop.drop && pc.bytes + bytes > cache_budget) return false;
+    pc.bytes += bytes;
+    return true;
+  };
+  {
+    prof::Section prof_integrate("ms.integrate_psf");
+    data_image.GetIntegratedPsf(integrated.F(), psfs);
+  }
+  const bool cache_hit =
+      !cache_drop.drop && PsfCacheHit(session, width, height, n_psf, integrated.F(), psfs);
+  if (!cache_hit) {
+    prof::Section prof_psfs("ms.convolve_psfs");
+    pc = PsfCache();
+    pc.session = &session;
+    pc.width = width;
+    pc.height = height;
+    pc.n_psf = n_psf;
+    for (const ScaleInfo& e : scale_infos_) pc.scales.push_back(e.scale);
+    pc.shape = settings_.shape;
+    pc.convolution_padding = settings_.convolution_padding;
+    pc.correction_f64 = SubMinorLoop::CorrectionF64();
+    pc.correction_kernel_f32 = SubMinorLoop::CorrectionKernelF32();
+    pc.psf_peak.assign(n_scales, 0.0f);
+    pc.convolved.resize(n_psf);
+    auto convolve_psfs = [&](gpu::Planes& out, const float* d_psf, bool is_integrated) {
+      out = gpu::Planes::Make(session, width, height, n_scales);
+      for (size_t si = 0; si != n_scales; ++si) {
+        session.D2D(out.Plane(si), d_psf, plane_bytes);
+        if (scale_infos_[si].scale != 0.0f)
+          transforms_->Transform(out.Plane(si), scale_infos_[si].scale);
+        if (is_integrated)
+          pc.psf_peak[si] =
+              session.ReadFloat(out.Plane(si) + width / 2 + (height / 2) * width);
+      }
+    };
+    convolve_psfs(pc.convolved[0], integrated.F(), true);
+    if (n_psf > 1)
+      for (size_t i = 0; i != n_psf; ++i) convolve_psfs(pc.convolved[i], psfs.Plane(i), false);
+    // kept only whole: the convolved PSFs and the copies the next major
+    // iteration's PSFs are compared with
+    if (!cache_drop.drop) {
+      if (cache_takes((n_psf * n_scales + n_psf + 1) * plane_bytes)) {
+        pc.reference = gpu::Planes::Make(session, width, height, n_psf + 1);
+        session.D2D(pc.reference.Plane(0), integrated.F(), plane_bytes);
+        for (size_t i = 0; i != n_psf; ++i)
+          session.D2D(pc.reference.Plane(1 + i), psfs.Plane(i), plane_bytes);
+      } else {
+        cache_drop.drop = true;
+      }
+    }
+  }
+  {
     const double first_auto_scale_size = beam_size_in_pixels_ * 2.0;
     for (size_t si = 0; si != n_scales; ++si) {
       ScaleInfo& e = scale_infos_[si];
-      session.D2D(out.Plane(si), d_psf, npx * sizeof(float));
-      if (e.scale != 0.0f) transforms_->Transform(out.Plane(si), e.scale);
-      if (is_integrated) {
-        e.psf_peak = session.ReadFloat(out.Plane(si) + width / 2 +
-                                       (height / 2) * width);
-        double exp_term;
-        if (e.scale == 0.0f || n_scales < 2)
-          exp_term = 0.0;
-        else
-          exp_term = std::log2(e.scale / first_auto_scale_size);
-        e.bias_factor = float(std::pow(settings_.scale_bias, -exp_term));
-        e.gain = float(double(MinorLoopGain()) / e.psf_peak);
-        e.is_active = true;
-        log::Info() << "- Scale " << std::round(e.scale)
-                    << ", bias factor=" << std::round(e.bias_factor * 10.0) / 10.0
-                    << ", psfpeak=" << e.psf_peak << ", gain=" << e.gain
-                    << ", kernel peak=" << e.kernel_peak << '\n';
-      }
+      e.psf_peak = pc.psf_peak[si];
+      double exp_term;
+      if (e.scale == 0.0f || n_scales < 2)
+        exp_term = 0.0;
+      else
+        exp_term = std::log2(e.scale / first_auto_scale_size);
+      e.bias_factor = float(std::pow(settings_.scale_bias, -exp_term));
+      e.gain = float(double(MinorLoopGain()) / e.psf_peak);
+      e.is_active = true;
+      log::Info() << "- Scale " << std::round(e.scale)
+                  << ", bias factor=" << std::round(e.bias_factor * 10.0) / 10.0
+                  << ", psfpeak=" << e.psf_peak << ", gain=" << e.gain
+                  << ", kernel peak=" << e.kernel_peak << '\n';
     }
-  };
-  {
-    prof::Section prof_psfs("ms.convolve_psfs");
-    data_image.GetIntegratedPsf(integrated.F(), psfs);
-    convolve_psfs(convolved[0], integrated.F(), true);
-    if (n_psf > 1)
-      for (size_t i = 0; i != n_psf; ++i)
-        convolve_psfs(convolved[i], psfs.Plane(i), false);
   }
+  const std::vector<gpu::Planes>& convolved = pc.convolved;
 
   FindActiveScaleConvolvedMaxima(data_image, integrated.F(), true);
   DeconvolutionResult result;
@@ -630,8 +755,9 @@ DeconvolutionResult MultiScaleAlgorithm::ExecuteMajorIteration(
               << (is_final_threshold ? " (final)\n" : "\n");
 
   ImageSet individual(data_image, width, height);
-  std::map<size_t, gpu::Planes> twice_cache;
-  std::map<std::pair<size_t, size_t>, std::shared_ptr<gpu::Buffer>> padded_cache;
+  // the twice-convolved PSFs and padded PSF spectra that did not fit the cache
+  std::map<size_t, gpu::Planes> twice_local;
+  std::map<std::pair<size_t, size_t>, std::shared_ptr<gpu::Buffer>> padded_local;
   bool diverging = false;
 
   while (IterationNumber() < MaxIterations() &&
@@ -642,19 +768,23 @@ DeconvolutionResult MultiScaleAlgorithm::ExecuteMajorIteration(
          threshold_countdown > 0 && !diverging) {  // :323-543
     ScaleInfo& info = scale_infos_[scale_with_peak];
     bool searched = false;  // the next peak searches already ran (deferred result)
-    // twice-convolved PSFs for this scale (:331-350), cached per major iteration
-    auto tw = twice_cache.find(scale_with_peak);
-    if (tw == twice_cache.end()) {
+    // twice-convolved PSFs for this scale (:331-350), made when first used
+    const gpu::Planes* twice_found = nullptr;
+    if (auto tw = pc.twice.find(scale_with_peak); tw != pc.twice.end())
+      twice_found = &tw->second;
+    else if (auto tl = twice_local.find(scale_with_peak); tl != twice_local.end())
+      twice_found = &tl->second;
+    if (!twice_found) {
       prof::Section prof_twice("ms.twice_convolved");
       gpu::Planes t = gpu::Planes::Make(session, width, height, n_psf);
       for (size_t i = 0; i != n_psf; ++i) {
-        session.D2D(t.Plane(i), convolved[i].Plane(scale_with_peak),
-                    npx * sizeof(float));
+        session.D2D(t.Plane(i), convolved[i].Plane(scale_with_peak), plane_bytes);
         if (info.scale != 0.0f) transforms_->Transform(t.Plane(i), info.scale);
       }
-      tw = twice_cache.emplace(scale_with_peak, std::move(t)).first;
+      auto& into = cache_takes(n_psf * plane_bytes) ? pc.twice : twice_local;
+      twice_found = &into.emplace(scale_with_peak, std::move(t)).first->second;
     }
-    const gpu::Planes& twice = tw->second;
+    const gpu::Planes& twice = *twice_found;
     // individually convolved images (:336-354); at scale 0 the fast sub-minor
     // loop only reads them, so it reads the residual itself
     const bool alias_residual = settings_.fast_sub_minor_loop && info.scale == 0.0f;
@@ -749,46 +879,84 @@ DeconvolutionResult MultiScaleAlgorithm::ExecuteMajorIteration(
       std::optional<prof::Section> prof_correct(std::in_place, "ms.correct_and_model");
       if (track_masks_ && scale_with_peak < dev_masks_.size())  // :444-445
         sub.UpdateAutoMask(static_cast<uint8_t*>(dev_masks_[scale_with_peak].Ptr()));
+      // The scales of the next searches (:521) follow from the previous
+      // searches' results alone, so they are known before the correction is
+      // queued. With scale 0 among them, and one image that is its own
+      // integrated image searched unweighted, the correction's inverse row
+      // pass makes that search over the residual values as it writes them
+      // (peak slot 0) instead of a pass that reads the residual again.
+      ActivateScales(scale_with_peak);
+      std::optional<gpu::PeakRequest> scale0_peak;
+      if (CorrPeakOn() && data_image.Size() == 1 &&
+          data_image.Integration(false).copy_fast_path && !RmsFactorImage())
+        for (size_t si = 0; si != n_scales; ++si)
+          if (scale_infos_[si].is_active && scale_infos_[si].scale == 0.0f) {
+            gpu::PeakRequest& q = scale0_peak.emplace();
+            q.h_border = uint32_t(std::round(width * CleanBorderRatio()));
+            q.v_border = uint32_t(std::round(height * CleanBorderRatio()));
+            q.allow_negative = AllowNegativeComponents();
+            q.d_mask = MaskFor(si);
+            q.slot = 0;
+            break;
+          }
+      // The scale > 0 model update: stamping the shape kernel costs
+      // n^2 multiply-adds per component (the stamping kernel skips the
+      // selected pixels whose model value stayed zero), against two
+      // full-image FFTs (:451-460 convolves with the same kernel). The
+      // loop's component count is known once its result is read, so a
+      // deferred loop's update is queued after that; the loop never reads
+      // the model image.
+      auto add_scale_model = [&](size_t i) {
+        size_t n_kernel = 0;
+        const float* d_kernel = transforms_->ShapeKernel(info.scale, n_kernel);
+        size_t n_stamps = sub.NSelected();
+        if (ModelGateOn()) n_stamps = std::min(n_stamps, IterationNumber() - sub_start);
+        if (double(n_stamps) * double(n_kernel) * double(n_kernel) <= 1e9) {
+          sub.AddShapeModel(i, d_kernel, n_kernel, model_image.Data(i));
+        } else {
+          sub.GetFullIndividualModel(i, scratch_->F());
+          transforms_->Transform(scratch_->F(), info.scale);
+          gpu::Check(rdl_add(s, model_image.Data(i), scratch_->F(), npx), "rdl_add");
+        }
+      };
+      const bool model_after_result = defer && ModelGateOn() && info.scale != 0.0f;
       for (size_t i = 0; i != data_image.Size(); ++i) {
         if (owner(i) != my_rank) continue;  // another rank's image
         const size_t psf_index = data_image.PsfIndex(i);
         auto key = std::make_pair(psf_index, scale_with_peak);
-        auto pc = padded_cache.find(key);
-        if (pc == padded_cache.end())
-          pc = padded_cache
-                   .emplace(key, SubMinorLoop::MakeCorrectionPsfSpectrum(
-                                     session, convolved[psf_index].Plane(scale_with_peak),
-                                     width, height, conv_w, conv_h))
-                   .first;
-        sub.CorrectResidualDirtyWithSpectrum(i, data_image.Data(i),
-                                             pc->second->Ptr());
-        if (info.scale != 0.0f) {
-          // the sub-minor model is a few hundred components: stamping the
-          // shape kernel costs n_sel * n^2 multiply-adds against two
-          // full-image FFTs (:451-460 convolves with the same kernel)
-          size_t n_kernel = 0;
-          const float* d_kernel = transforms_->ShapeKernel(info.scale, n_kernel);
-          if (double(sub.NSelected()) * double(n_kernel) * double(n_kernel) <= 1e9) {
-            sub.AddShapeModel(i, d_kernel, n_kernel, model_image.Data(i));
-          } else {
-            sub.GetFullIndividualModel(i, scratch_->F());
-            transforms_->Transform(scratch_->F(), info.scale);
-            gpu::Check(rdl_add(s, model_image.Data(i), scratch_->F(), npx),
-                       "rdl_add");
-          }
-        } else {
-          sub.AddIndividualModel(i, model_image.Data(i));
+        const gpu::Buffer* padded = nullptr;
+        if (auto it = pc.padded.find(key); it != pc.padded.end())
+          padded = it->second.get();
+        else if (auto il = padded_local.find(key); il != padded_local.end())
+          padded = il->second.get();
+        if (!padded) {
+          std::shared_ptr<gpu::Buffer> made = SubMinorLoop::MakeCorrectionPsfSpectrum(
+              session, convolved[psf_index].Plane(scale_with_peak), width, height, conv_w,
+              conv_h);
+          padded = made.get();
+          (cache_takes(made->Bytes()) ? pc.padded : padded_local).emplace(key, std::move(made));
         }
+        if (sub.CorrectResidualDirtyWithSpectrum(i, data_image.Data(i), padded->Ptr(),
+                                                 scale0_peak ? &*scale0_peak : nullptr))
+          scale0_search_queued_ = true;
+        if (info.scale == 0.0f)
+          sub.AddIndividualModel(i, model_image.Data(i));
+        else if (!model_after_result)
+          add_scale_model(i);
       }
       if (track_components_)  // :447-448
         sub.UpdateComponentList(*component_list_, scale_with_peak);
       prof_correct.reset();
       share_planes(data_image);  // the corrected residuals, from their owners
       if (defer) {
-        ActivateScales(scale_with_peak);
         FindActiveScaleConvolvedMaxima(data_image, integrated.F(), false);
         searched = true;
         account(sub.Collect());
+        if (model_after_result) {
+          prof::Section prof_model("ms.correct_and_model");
+          for (size_t i = 0; i != data_image.Size(); ++i)
+            if (owner(i) == my_rank) add_scale_model(i);
+        }
       }
     } else {  // :463-519
       size_t n_kernel = 0;

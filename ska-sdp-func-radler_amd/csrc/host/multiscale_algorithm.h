@@ -5,7 +5,8 @@
 // Device-side caching the reference does not do (results are the same
 // convolutions): the forward FFT of the integrated image is shared by all
 // active scales, twice-convolved PSFs and padded PSF spectra are computed once
-// per scale per major iteration.
+// per scale, and kept over the major iterations whose PSFs are the same
+// (PsfCache).
 #pragma once
 
 #include <map>
@@ -141,6 +142,39 @@ class MultiScaleAlgorithm final : public DeconvolutionAlgorithm {
   // per scale and swapped in instead of convolving again.
   std::vector<gpu::Planes> scale_images_;
   std::vector<bool> scale_image_valid_;
+  // The scale-0 search of the next FindActiveScaleConvolvedMaxima is already
+  // queued in peak slot 0: the residual correction's inverse row pass made it
+  // over the values it wrote (SubMinorLoop::CorrectResidualDirtyWithSpectrum
+  // with a PeakRequest), so the residual is not read again for it.
+  bool scale0_search_queued_ = false;
+
+  // The PSF-derived products of a major iteration, kept for the next one on a
+  // main session while the PSFs, the scales and the sizes stay the same (the
+  // PSF of a deconvolution does not change between its major iterations). A
+  // worker session's clones and RDL_PSF_CACHE=0 drop them on every return.
+  struct PsfCache {
+    // the key: everything the products depend on; the PSFs by content
+    // (`reference`: the integrated PSF, then every PSF plane, compared bit
+    // for bit on the device)
+    gpu::Session* session = nullptr;
+    size_t width = 0, height = 0, n_psf = 0;
+    std::vector<float> scales;
+    MultiscaleShape shape{};
+    double convolution_padding = 0.0;
+    bool correction_f64 = true, correction_kernel_f32 = false;
+    gpu::Planes reference;
+    // the products
+    std::vector<float> psf_peak;         // per scale (ConvolvePsfs, :29-88)
+    std::vector<gpu::Planes> convolved;  // [psf][scale]
+    std::map<size_t, gpu::Planes> twice;  // scale -> [psf], filled when first used
+    std::map<std::pair<size_t, size_t>, std::shared_ptr<gpu::Buffer>> padded;  // (psf, scale)
+    size_t bytes = 0;  // held by the above, against RDL_PSF_CACHE_MB
+  };
+  PsfCache psf_cache_;
+  /// whether psf_cache_ holds the products of these PSFs (queues the content
+  /// comparison and waits for it)
+  bool PsfCacheHit(gpu::Session& session, size_t width, size_t height, size_t n_psf,
+                   const float* d_integrated_psf, const gpu::Planes& psfs);
 
   bool track_masks_ = false, use_masks_ = false;
   std::vector<std::vector<uint8_t>> host_masks_;

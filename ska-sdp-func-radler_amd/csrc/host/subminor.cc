@@ -197,9 +197,10 @@ void SubMinorLoop::CorrectResidualDirty(size_t image_index, float* d_residual,
   CorrectResidualDirtyWithSpectrum(image_index, d_residual, it->second->Ptr());
 }
 
-void SubMinorLoop::CorrectResidualDirtyWithSpectrum(size_t image_index,
+bool SubMinorLoop::CorrectResidualDirtyWithSpectrum(size_t image_index,
                                                     float* d_residual,
-                                                    const void* d_spectrum) {
+                                                    const void* d_spectrum,
+                                                    const gpu::PeakRequest* peak) {
   gpu::Fft& fft = s_.GetFft(padded_width_, padded_height_, CorrectionF64());
   const uint32_t ox = uint32_t((padded_width_ - width_) / 2);
   const uint32_t oy = uint32_t((padded_height_ - height_) / 2);
@@ -222,10 +223,10 @@ void SubMinorLoop::CorrectResidualDirtyWithSpectrum(size_t image_index,
                                          uint32_t(width_), uint32_t(height_),
                                          static_cast<const uint8_t*>(rows.Ptr()), oy),
                "rdl_subminor_model_masked");
-    fft.ConvolveSubtract(model.F(), width_, height_, ox, oy, d_spectrum, work.Ptr(),
-                         d_residual, static_cast<const uint8_t*>(rows.Ptr()),
-                         !fft.SplitColumns(), CorrectionKernelF32() && fft.ConvColumnsD());
-    return;
+    return fft.ConvolveSubtract(model.F(), width_, height_, ox, oy, d_spectrum, work.Ptr(),
+                                d_residual, static_cast<const uint8_t*>(rows.Ptr()),
+                                !fft.SplitColumns(),
+                                CorrectionKernelF32() && fft.ConvColumnsD(), peak);
   }
   if (!fft.IsF64()) {  // rocFFT float (RDL_CORR_F32=1 at a size the LDS engine lacks)
     gpu::Buffer& padded = s_.Scratch(gpu::Session::kCorrectionSpectrum,
@@ -238,7 +239,7 @@ void SubMinorLoop::CorrectResidualDirtyWithSpectrum(size_t image_index,
                                  padded.F(), uint32_t(padded_width_),
                                  uint32_t(padded_height_)),
                "rdl_trim_subtract");
-    return;
+    return false;
   }
   gpu::Buffer& padded_ = s_.Scratch(gpu::Session::kCorrectionSpectrum,
                                     padded_width_ * padded_height_ * sizeof(double));
@@ -254,6 +255,7 @@ void SubMinorLoop::CorrectResidualDirtyWithSpectrum(size_t image_index,
                                    uint32_t(padded_width_),
                                    uint32_t(padded_height_)),
              "rdl_trim_subtract_f64");
+  return false;
 }
 
 void SubMinorLoop::GetFullIndividualModel(size_t image_index, float* d_dest) {

@@ -70,8 +70,12 @@ class SubMinorLoop {
                             const float* d_single_convolved_psf,
                             size_t psf_key);
   /// The same with a caller-cached padded PSF spectrum (MakePaddedPsfSpectrum).
-  void CorrectResidualDirtyWithSpectrum(size_t image_index, float* d_residual,
-                                        const void* d_psf_spectrum);
+  /// With `peak`: the peak search of the corrected residual fused into the
+  /// correction's last pass where the plan has that form; returns whether
+  /// the search was queued (false: search the residual as before).
+  bool CorrectResidualDirtyWithSpectrum(size_t image_index, float* d_residual,
+                                        const void* d_psf_spectrum,
+                                        const gpu::PeakRequest* peak = nullptr);
   static std::shared_ptr<gpu::Buffer> MakePaddedPsfSpectrum(
       gpu::Session& s, const float* d_psf, size_t width, size_t height,
       size_t padded_width, size_t padded_height, bool f64 = true);
