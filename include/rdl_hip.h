@@ -379,6 +379,35 @@ int rdl_forced_interpolate(rdl_session* s, const float* d_in, size_t in_stride,
                            const rdl_forced_terms* forced, const double* out_lg,
                            uint32_t n_out, float* d_out, size_t out_stride);
 
+/* ---------------------------------------- component list: batched term fit */
+/* The fit of ComponentList::Write (cpp/component_list.cc:105-117): the
+ * spectral terms of n_components channel spectra, one lane per component.
+ * d_values is channel-major (channel c of component i at
+ * d_values + c * value_stride + i) and d_terms term-major in the same way
+ * (n_terms planes, term_stride floats apart), so a wave reads and writes
+ * consecutive floats. By mode:
+ *   RDL_TERMS_POLYNOMIAL  terms[t] = float(sum_c h_fit[t * n_channels + c] *
+ *                         double(v_c)) over the channels with h_fitted[c] != 0,
+ *                         in channel order (SpectralFitter::Fit's linear map;
+ *                         n_channels, n_terms <= RDL_MAX_IMAGES);
+ *   RDL_TERMS_LOGPOLY     the log-polynomial fit described by `fit`;
+ *   RDL_TERMS_FORCED      terms 1.. are read from `forced`'s planes at the
+ *                         component's pixel (h_x[i], h_y[i]) and term 0 fitted.
+ * For the last two n_channels and n_terms must equal fit's. Only the forced
+ * mode reads the positions; they are host arrays because every one of them is
+ * checked against width x height, and the planes against that image, before
+ * anything is launched. h_fit / h_fitted, fit and forced may be NULL in the
+ * modes that do not use them. n_components == 0 does nothing. */
+#define RDL_TERMS_POLYNOMIAL 0u
+#define RDL_TERMS_LOGPOLY 1u
+#define RDL_TERMS_FORCED 2u
+int rdl_component_terms(rdl_session* s, uint32_t mode, uint32_t n_channels,
+                        uint32_t n_terms, const double* h_fit, const uint8_t* h_fitted,
+                        const rdl_logpoly* fit, const rdl_forced_terms* forced,
+                        uint32_t width, uint32_t height, const uint32_t* h_x,
+                        const uint32_t* h_y, const float* d_values, size_t value_stride,
+                        size_t n_components, float* d_terms, size_t term_stride);
+
 /* ---------------------------------------------------------------- Högbom */
 typedef struct {
   uint32_t width, height;

@@ -7,6 +7,7 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstring>
 #include <memory>
@@ -165,6 +166,53 @@ struct ImageCoordinates {
     const T mid_x = T(width) / T(2), mid_y = T(height) / T(2);
     l = (mid_x - T(x)) * pixel_size_x;
     m = (T(y) - mid_y) * pixel_size_y;
+  }
+  // the direction (l, m) seen from phase centre (ra0, dec0)
+  template <typename T>
+  static void LMToRaDec(T l, T m, T phase_centre_ra, T phase_centre_dec, T& ra, T& dec) {
+    const T n = std::sqrt(T(1) - l * l - m * m);
+    const T cos_dec0 = std::cos(phase_centre_dec), sin_dec0 = std::sin(phase_centre_dec);
+    ra = phase_centre_ra + std::atan2(l, n * cos_dec0 - m * sin_dec0);
+    dec = std::asin(m * cos_dec0 + n * sin_dec0);
+  }
+};
+
+// aocommon/radeccoord.h, the two formatters the source catalogue uses
+// (restated from their published behaviour; parity unpinned — DESIGN.md)
+struct RaDecCoord {
+  /// HH:MM:SS.sss of fmod(ra, 24 h), rounded to 1/1000 s; a negative angle
+  /// keeps its sign (it is not wrapped to 0..24 h)
+  static std::string RAToString(long double ra, char delimiter) {
+    constexpr long double kPi = 3.141592653589793238462643383279502884L;
+    const long double hours = std::fmod(ra * (12.0L / kPi), 24.0L);
+    return Sexagesimal(hours, delimiter);
+  }
+  /// DD.MM.SS.sss, rounded to 1/1000 arcsec; '-' when negative, no '+'
+  static std::string DecToString(long double dec, char delimiter) {
+    constexpr long double kPi = 3.141592653589793238462643383279502884L;
+    return Sexagesimal(dec * (180.0L / kPi), delimiter);
+  }
+
+ private:
+  static std::string Sexagesimal(long double units, char delimiter) {
+    const long long parts = std::llround(std::fabs(units) * 3600000.0L);
+    const long long whole = parts / 3600000, minutes = parts / 60000 % 60,
+                    seconds = parts / 1000 % 60, milli = parts % 1000;
+    std::string s;
+    if (units < 0.0L && parts != 0) s += '-';
+    if (whole < 10) s += '0';
+    s += std::to_string(whole);
+    s += delimiter;
+    s += char('0' + minutes / 10);
+    s += char('0' + minutes % 10);
+    s += delimiter;
+    s += char('0' + seconds / 10);
+    s += char('0' + seconds % 10);
+    s += '.';
+    s += char('0' + milli / 100);
+    s += char('0' + milli / 10 % 10);
+    s += char('0' + milli % 10);
+    return s;
   }
 };
 

@@ -1,9 +1,24 @@
 #include "component_list.h"
 
 #include <algorithm>
+#include <cmath>
+#include <fstream>
+#include <iomanip>
+#include <limits>
+#include <memory>
 #include <numeric>
+#include <stdexcept>
 
+#ifdef RADLER_AMD_USE_EXTERNAL_AOCOMMON
+#include <aocommon/imagecoordinates.h>
+#include <aocommon/radeccoord.h>
+#endif
+
+#include "device.h"
 #include "image_set.h"
+#include "multiscale_algorithm.h"
+#include "radler.h"
+#include "spectral_fitter.h"
 
 namespace radler {
 
@@ -106,6 +121,292 @@ void ComponentList::MultiplyScaleComponent(size_t scale_index, size_t position_i
 void ComponentList::SetValues(size_t scale_index, size_t index, const float* values) {
   std::copy_n(values, n_frequencies_,
               &list_per_scale_[scale_index].values[index * n_frequencies_]);
+}
+
+// ------------------------------------------------------- source catalogue
+namespace {
+
+using schaapcommon::fitters::SpectralFitter;
+using schaapcommon::fitters::SpectralFittingMode;
+
+constexpr int kFloatDigits = std::numeric_limits<float>::digits10 + 1;    // 7
+constexpr int kDoubleDigits = std::numeric_limits<double>::digits10 + 1;  // 16
+
+// cpp/utils/write_model.h: the text format of a source catalogue
+void WriteHeader(std::ostream& stream, double reference_frequency) {
+  stream.precision(kDoubleDigits);
+  stream << "Format = Name, Type, Ra, Dec, I, SpectralIndex, LogarithmicSI, "
+            "ReferenceFrequency='"
+         << reference_frequency << "', MajorAxis, MinorAxis, Orientation\n";
+}
+
+// name,TYPE,ra,dec,t0,[t1,...],true|false,ref, then the shape: empty fields
+// for a point, major and minor axis (arcsec) and orientation for a Gaussian
+void WriteRow(std::ostream& stream, size_t scale_index, size_t component_index,
+              bool gaussian, long double ra, long double dec, const float* terms,
+              size_t n_terms, bool use_log_si, double reference_frequency, double major,
+              double minor) {
+  stream << 's' << scale_index << 'c' << component_index
+         << (gaussian ? ",GAUSSIAN," : ",POINT,") << aocommon::RaDecCoord::RAToString(ra, ':')
+         << ',' << aocommon::RaDecCoord::DecToString(dec, '.') << ',';
+  stream << std::setprecision(kFloatDigits) << terms[0] << ",[";
+  for (size_t t = 1; t < n_terms; ++t) {
+    if (t != 1) stream << ',';
+    stream << terms[t];
+  }
+  stream << ']';
+  stream.precision(kDoubleDigits);
+  stream << ',' << (use_log_si ? "true" : "false") << ',' << reference_frequency << ',';
+  if (gaussian)
+    stream << major << ',' << minor << ',' << 0.0 << '\n';
+  else
+    stream << ",,\n";
+}
+
+}  // namespace
+
+size_t ComponentList::TermCount(const SpectralFitter& fitter) const {
+  return n_frequencies_ == 1 ? 1 : fitter.NTerms();
+}
+
+void ComponentList::CheckWritable(const SpectralFitter& fitter) const {
+  if (added_since_merge_ != 0)
+    throw std::runtime_error(
+        "ComponentList::Write called while there are yet unmerged components. "
+        "Run ComponentList::MergeDuplicates() first.");
+  if (fitter.Mode() == SpectralFittingMode::kNoFitting && n_frequencies_ > 1)
+    throw std::runtime_error(
+        "Can't Write component list, because you have not specified a spectral "
+        "fitting method. You probably want to add '-fit-spectral-pol'.");
+  if (n_frequencies_ > 1 && fitter.Frequencies().size() != n_frequencies_)
+    throw std::runtime_error(
+        "Can't Write component list: its components have " +
+        std::to_string(n_frequencies_) + " frequencies, the spectral fitter has " +
+        std::to_string(fitter.Frequencies().size()) + " channels");
+  if (n_frequencies_ > 1 && fitter.NTerms() == 0)
+    throw std::runtime_error("Can't Write component list: the spectral fitter has no terms");
+}
+
+// What the device fit of one Write needs, made once and used for every
+// scale: the fitter's description and, for a forced fit, the term planes on
+// the device (one upload, however many scales the list has).
+struct ComponentList::DeviceFit {
+  gpu::Session& session;
+  uint32_t mode = RDL_TERMS_POLYNOMIAL;
+  std::vector<double> map;      // polynomial: n_terms x n_channels
+  std::vector<uint8_t> fitted;  // polynomial: channel has weight > 0
+  rdl_logpoly fit{};            // log-polynomial, forced
+  rdl_forced_terms forced{};    // forced
+  gpu::Buffer planes;           // forced: what forced.d_planes points at
+};
+
+std::unique_ptr<ComponentList::DeviceFit> ComponentList::MakeDeviceFit(
+    const SpectralFitter& fitter, gpu::Session& session, const ForcedTermImages* images) const {
+  auto fit = std::make_unique<DeviceFit>(DeviceFit{session});
+  session.Bind();
+  switch (fitter.Mode()) {
+    case SpectralFittingMode::kNoFitting:
+      break;  // CheckWritable: a single frequency, nothing is fitted
+    case SpectralFittingMode::kPolynomial:
+      fit->mode = RDL_TERMS_POLYNOMIAL;
+      fit->map = MakeSpectralMaps(fitter).fit;
+      fit->fitted.resize(n_frequencies_);
+      for (size_t c = 0; c != n_frequencies_; ++c)
+        fit->fitted[c] = c < fitter.Weights().size() && fitter.Weights()[c] > 0.0f;
+      break;
+    case SpectralFittingMode::kLogPolynomial:
+      fit->mode = RDL_TERMS_LOGPOLY;
+      MakeLogPoly(fitter, &fit->fit);
+      break;
+    case SpectralFittingMode::kForcedTerms: {
+      fit->mode = RDL_TERMS_FORCED;
+      MakeForcedLogPoly(fitter, &fit->fit, fit->forced.weights);
+      if (fitter.NTerms() <= 1) break;
+      // full-image planes: the algorithm's (contiguous), or the fitter's own
+      std::vector<const float*> planes;
+      size_t width = 0, plane = 0;
+      if (images) {
+        width = images->width;
+        plane = images->width * images->height;
+        for (size_t k = 0; k != images->n_planes; ++k)
+          planes.push_back(images->data.data() + k * plane);
+      }
+#ifndef RADLER_AMD_USE_EXTERNAL_AOCOMMON
+      else {
+        width = fitter.ForcedWidth();
+        for (const std::vector<float>& p : fitter.ForcedPlanes()) {
+          planes.push_back(p.data());
+          plane = p.size();
+        }
+      }
+#endif
+      if (planes.size() + 1 != fitter.NTerms() || width == 0)
+        throw std::runtime_error(
+            "ComponentList::Write: forced-term fitting needs the term planes of the image");
+      fit->planes = gpu::Buffer(session, planes.size() * plane * sizeof(float));
+      for (size_t k = 0; k != planes.size(); ++k)
+        session.H2D(fit->planes.F() + k * plane, planes[k], plane * sizeof(float));
+      fit->forced.d_planes = fit->planes.F();
+      fit->forced.plane_stride = plane;
+      fit->forced.pitch = uint32_t(width);
+      fit->forced.rows = uint32_t(plane / width);
+      break;
+    }
+  }
+  return fit;
+}
+
+std::vector<float> ComponentList::FitTermsOnDevice(size_t scale_index, size_t n_terms,
+                                                   const DeviceFit& fit) const {
+  const ScaleList& list = list_per_scale_[scale_index];
+  const size_t n = list.positions.size();
+  std::vector<float> terms(n * n_terms);
+  if (n == 0) return terms;
+  // channel-major spectra in, term-major terms out
+  gpu::Session& s = fit.session;
+  s.Bind();
+  std::vector<float> staged(n * std::max(n_frequencies_, n_terms));
+  for (size_t i = 0; i != n; ++i)
+    for (size_t f = 0; f != n_frequencies_; ++f)
+      staged[f * n + i] = list.values[i * n_frequencies_ + f];
+  gpu::Buffer d_values(s, n * n_frequencies_ * sizeof(float)),
+      d_terms(s, n * n_terms * sizeof(float));
+  s.H2D(d_values.Ptr(), staged.data(), n * n_frequencies_ * sizeof(float));
+  std::vector<uint32_t> xy;
+  if (fit.mode == RDL_TERMS_FORCED) {
+    xy.resize(2 * n);
+    for (size_t i = 0; i != n; ++i) {
+      xy[i] = uint32_t(list.positions[i].x);
+      xy[n + i] = uint32_t(list.positions[i].y);
+    }
+  }
+  gpu::Check(rdl_component_terms(s.Handle(), fit.mode, uint32_t(n_frequencies_),
+                                 uint32_t(n_terms), fit.map.data(), fit.fitted.data(), &fit.fit,
+                                 &fit.forced, uint32_t(width_), uint32_t(height_), xy.data(),
+                                 xy.empty() ? nullptr : xy.data() + n, d_values.F(), n, n,
+                                 d_terms.F(), n),
+             "rdl_component_terms");
+  s.D2H(staged.data(), d_terms.Ptr(), n * n_terms * sizeof(float));
+  for (size_t i = 0; i != n; ++i)
+    for (size_t t = 0; t != n_terms; ++t) terms[i * n_terms + t] = staged[t * n + i];
+  return terms;
+}
+
+std::vector<float> ComponentList::FitTermsOnHost(size_t scale_index, size_t n_terms,
+                                                 const SpectralFitter& fitter) const {
+  const ScaleList& list = list_per_scale_[scale_index];
+  const size_t n = list.positions.size();
+  std::vector<float> terms(n * n_terms), one;
+  for (size_t i = 0; i != n; ++i) {
+    fitter.Fit(one, &list.values[i * n_frequencies_], list.positions[i].x, list.positions[i].y);
+    std::copy_n(one.begin(), n_terms, &terms[i * n_terms]);
+  }
+  return terms;
+}
+
+std::vector<float> ComponentList::FitTerms(size_t scale_index, const SpectralFitter& fitter,
+                                           gpu::Session* session) const {
+  CheckWritable(fitter);
+  if (n_frequencies_ == 1) return list_per_scale_[scale_index].values;
+  if (!session) return FitTermsOnHost(scale_index, TermCount(fitter), fitter);
+  return FitTermsOnDevice(scale_index, TermCount(fitter),
+                          *MakeDeviceFit(fitter, *session, nullptr));
+}
+
+void ComponentList::WriteSources(const Radler& radler, const std::string& filename,
+                                 long double pixel_scale_x, long double pixel_scale_y,
+                                 long double phase_centre_ra, long double phase_centre_dec,
+                                 long double l_shift, long double m_shift) const {
+  const algorithms::DeconvolutionAlgorithm& algorithm = radler.MaxScaleCountAlgorithm();
+  std::vector<double> scale_sizes(NScales(), 0.0);
+  if (const auto* multiscale = dynamic_cast<const algorithms::MultiScaleAlgorithm*>(&algorithm))
+    for (size_t i = 0; i != NScales(); ++i) scale_sizes[i] = multiscale->ScaleSize(i);
+  else
+    scale_sizes.assign(1, 0.0);
+  const SpectralFitter& fitter = algorithm.Fitter();
+  // nothing is fitted for a single frequency
+  gpu::Session* session = n_frequencies_ > 1 ? &radler.DeviceSession() : nullptr;
+  // the algorithm, not its fitter, holds the full-image term planes of a forced fit
+  WriteRows(filename, fitter, scale_sizes, pixel_scale_x, pixel_scale_y, phase_centre_ra,
+            phase_centre_dec, l_shift, m_shift, session, algorithm.SpectrallyForcedImages().get());
+}
+
+void ComponentList::Write(const std::string& filename,
+                          const algorithms::MultiScaleAlgorithm& multiscale,
+                          long double pixel_scale_x, long double pixel_scale_y,
+                          long double phase_centre_ra, long double phase_centre_dec,
+                          long double l_shift, long double m_shift) const {
+  std::vector<double> scale_sizes(NScales());
+  for (size_t i = 0; i != NScales(); ++i) scale_sizes[i] = multiscale.ScaleSize(i);
+  Write(filename, multiscale.Fitter(), scale_sizes, pixel_scale_x, pixel_scale_y,
+        phase_centre_ra, phase_centre_dec, l_shift, m_shift);
+}
+
+void ComponentList::WriteSingleScale(const std::string& filename,
+                                     const algorithms::DeconvolutionAlgorithm& algorithm,
+                                     long double pixel_scale_x, long double pixel_scale_y,
+                                     long double phase_centre_ra, long double phase_centre_dec,
+                                     long double l_shift, long double m_shift) const {
+  Write(filename, algorithm.Fitter(), std::vector<double>(1, 0.0), pixel_scale_x, pixel_scale_y,
+        phase_centre_ra, phase_centre_dec, l_shift, m_shift);
+}
+
+void ComponentList::Write(const std::string& filename, const SpectralFitter& fitter,
+                          const std::vector<double>& scale_sizes, long double pixel_scale_x,
+                          long double pixel_scale_y, long double phase_centre_ra,
+                          long double phase_centre_dec, long double l_shift,
+                          long double m_shift, gpu::Session* session) const {
+  WriteRows(filename, fitter, scale_sizes, pixel_scale_x, pixel_scale_y, phase_centre_ra,
+            phase_centre_dec, l_shift, m_shift, session, nullptr);
+}
+
+void ComponentList::WriteRows(const std::string& filename, const SpectralFitter& fitter,
+                              const std::vector<double>& scale_sizes,
+                              long double pixel_scale_x, long double pixel_scale_y,
+                              long double phase_centre_ra, long double phase_centre_dec,
+                              long double l_shift, long double m_shift, gpu::Session* session,
+                              const ForcedTermImages* images) const {
+  CheckWritable(fitter);
+  std::unique_ptr<DeviceFit> device_fit;
+  if (session && n_frequencies_ > 1) device_fit = MakeDeviceFit(fitter, *session, images);
+  if (scale_sizes.size() < NScales())
+    throw std::runtime_error("ComponentList::Write: " + std::to_string(scale_sizes.size()) +
+                             " scale sizes given for " + std::to_string(NScales()) +
+                             " scales");
+  const bool use_log_si = fitter.Mode() == SpectralFittingMode::kLogPolynomial ||
+                          fitter.Mode() == SpectralFittingMode::kForcedTerms;
+  const size_t n_terms = TermCount(fitter);
+  const double reference = fitter.ReferenceFrequency();
+  std::ofstream file(filename);
+  if (!file) throw std::runtime_error("ComponentList::Write: can't open " + filename);
+  WriteHeader(file, reference);
+  for (size_t scale_index = 0; scale_index != NScales(); ++scale_index) {
+    const ScaleList& list = list_per_scale_[scale_index];
+    const double scale = scale_sizes[scale_index];
+    // the FWHM of the scale's Gaussian, in arcsec along each axis
+    const double fwhm =
+        2.0L * std::sqrt(2.0L * std::log(2.0L)) *
+        algorithms::multiscale::MultiScaleTransforms::GaussianSigma(scale);
+    const double major = fwhm * pixel_scale_x * (180.0 * 60.0 * 60.0 / M_PI),
+                 minor = fwhm * pixel_scale_y * (180.0 * 60.0 * 60.0 / M_PI);
+    const std::vector<float> terms =
+        n_frequencies_ == 1 ? list.values
+        : device_fit        ? FitTermsOnDevice(scale_index, n_terms, *device_fit)
+                            : FitTermsOnHost(scale_index, n_terms, fitter);
+    for (size_t index = 0; index != list.positions.size(); ++index) {
+      const size_t x = list.positions[index].x, y = list.positions[index].y;
+      long double l, m, ra, dec;
+      aocommon::ImageCoordinates::XYToLM<long double>(x, y, pixel_scale_x, pixel_scale_y,
+                                                      width_, height_, l, m);
+      l += l_shift;
+      m += m_shift;
+      aocommon::ImageCoordinates::LMToRaDec<long double>(l, m, phase_centre_ra,
+                                                         phase_centre_dec, ra, dec);
+      WriteRow(file, scale_index, index, scale != 0.0, ra, dec, &terms[index * n_terms],
+               n_terms, use_log_si, reference, major, minor);
+    }
+  }
+  if (!file) throw std::runtime_error("ComponentList::Write: writing " + filename + " failed");
 }
 
 void ComponentList::Clear() {

@@ -4,12 +4,33 @@
 #pragma once
 
 #include <cstddef>
+#include <memory>
+#include <string>
 #include <utility>
 #include <vector>
+
+#include "aocommon_compat.h"
+
+#ifndef RADLER_AMD_USE_EXTERNAL_AOCOMMON
+namespace schaapcommon::fitters {
+class SpectralFitter;
+}
+#else
+#include <schaapcommon/fitters/spectralfitter.h>
+#endif
 
 namespace radler {
 
 class ImageSet;
+class Radler;
+struct ForcedTermImages;
+namespace algorithms {
+class DeconvolutionAlgorithm;
+class MultiScaleAlgorithm;
+}  // namespace algorithms
+namespace gpu {
+class Session;
+}
 
 class ComponentList {
  public:
@@ -60,12 +81,73 @@ class ComponentList {
     return list_per_scale_[scale_index].positions;
   }
 
+  /// component_list.cc:15-32: the list as a source catalogue (text), with the
+  /// scale sizes and the spectral fitter of the Radler's algorithm. The
+  /// spectral terms are fitted on the Radler's device session: in every
+  /// fitting mode the batched fit, with its staging, its copies and (forced)
+  /// one upload of term planes of the image's size, is faster than the host
+  /// loop at the list sizes of a deep clean (profiles/component_terms_fit.txt).
+  void WriteSources(const Radler& radler, const std::string& filename,
+                    long double pixel_scale_x, long double pixel_scale_y,
+                    long double phase_centre_ra, long double phase_centre_dec,
+                    long double l_shift = 0.0, long double m_shift = 0.0) const;
+  /// component_list.cc:34-57
+  void Write(const std::string& filename, const algorithms::MultiScaleAlgorithm& multiscale,
+             long double pixel_scale_x, long double pixel_scale_y,
+             long double phase_centre_ra, long double phase_centre_dec,
+             long double l_shift = 0.0, long double m_shift = 0.0) const;
+  void WriteSingleScale(const std::string& filename,
+                        const algorithms::DeconvolutionAlgorithm& algorithm,
+                        long double pixel_scale_x, long double pixel_scale_y,
+                        long double phase_centre_ra, long double phase_centre_dec,
+                        long double l_shift = 0.0, long double m_shift = 0.0) const;
+  /// component_list.cc:59-140. One row per component: POINT for a scale of
+  /// size 0, GAUSSIAN otherwise. Without a session every component is fitted
+  /// by fitter.Fit on the host, as the reference does; with one, a scale's
+  /// components are fitted in one batch on the device
+  /// (rdl_component_terms). The rows are formatted by the same code, so the
+  /// two files differ in nothing but the fitted terms. Unlike the reference
+  /// this throws when the list has several frequencies and the fitter has
+  /// another number of channels (the reference fits a spectrum of the wrong
+  /// length).
+  void Write(const std::string& filename,
+             const schaapcommon::fitters::SpectralFitter& fitter,
+             const std::vector<double>& scale_sizes, long double pixel_scale_x,
+             long double pixel_scale_y, long double phase_centre_ra,
+             long double phase_centre_dec, long double l_shift = 0.0,
+             long double m_shift = 0.0, gpu::Session* session = nullptr) const;
+  /// The terms Write gives the components of a scale, component by component
+  /// (TermCount(fitter) floats each); the same two paths.
+  std::vector<float> FitTerms(size_t scale_index,
+                              const schaapcommon::fitters::SpectralFitter& fitter,
+                              gpu::Session* session = nullptr) const;
+  /// Terms per component: the fitter's, or 1 for a single-frequency list
+  /// (its value is its only term and nothing is fitted).
+  size_t TermCount(const schaapcommon::fitters::SpectralFitter& fitter) const;
+
  private:
   struct ScaleList {
     std::vector<Position> positions;
     std::vector<float> values;
   };
   void MergeDuplicates(size_t scale_index);
+  void CheckWritable(const schaapcommon::fitters::SpectralFitter& fitter) const;
+  struct DeviceFit;
+  /// `images`: the full-image term planes of a forced fit on the device when
+  /// the fitter does not hold them itself (a Radler's algorithm keeps them)
+  std::unique_ptr<DeviceFit> MakeDeviceFit(const schaapcommon::fitters::SpectralFitter& fitter,
+                                           gpu::Session& session,
+                                           const ForcedTermImages* images) const;
+  std::vector<float> FitTermsOnDevice(size_t scale_index, size_t n_terms,
+                                      const DeviceFit& fit) const;
+  std::vector<float> FitTermsOnHost(size_t scale_index, size_t n_terms,
+                                    const schaapcommon::fitters::SpectralFitter& fitter) const;
+  void WriteRows(const std::string& filename,
+                 const schaapcommon::fitters::SpectralFitter& fitter,
+                 const std::vector<double>& scale_sizes, long double pixel_scale_x,
+                 long double pixel_scale_y, long double phase_centre_ra,
+                 long double phase_centre_dec, long double l_shift, long double m_shift,
+                 gpu::Session* session, const ForcedTermImages* images) const;
   size_t width_ = 0, height_ = 0, n_frequencies_ = 0;
   size_t added_since_merge_ = 0;
   std::vector<ScaleList> list_per_scale_;

@@ -16,6 +16,7 @@
 #include "dijkstra_splitter.h"
 #include "image_accessors.h"
 #include "logger.h"
+#include "multiscale_algorithm.h"
 #include "radler.h"
 #include "rms_image.h"
 #include "component_optimization.h"
@@ -179,6 +180,16 @@ void InitSpectralFitter(py::module& m) {
       .def_property_readonly("frequencies", &SpectralFitter::Frequencies)
       .def_property_readonly("weights", &SpectralFitter::Weights)
       .def_property_readonly("reference_frequency", &SpectralFitter::ReferenceFrequency)
+      .def_property_readonly(
+          "fit_matrix",
+          [](const SpectralFitter& self) {
+            // polynomial mode: the (n_terms, channels) float64 map fit() applies
+            // to the channels with weight > 0 (empty in the other modes)
+            const radler::SpectralMaps maps = radler::MakeSpectralMaps(self);
+            py::array_t<double> out({maps.n_terms, maps.n_channels});
+            std::copy(maps.fit.begin(), maps.fit.end(), out.mutable_data());
+            return out;
+          })
       .def("fit",
            [](const SpectralFitter& self, const std::vector<float>& values, size_t x,
               size_t y) {
@@ -428,7 +439,23 @@ void InitRadler(py::module& m) {  // python/pyradler.cc
            py::arg("major_iteration_number"))
       .def("set_communicator", &radler::Radler::SetCommunicator, py::arg("communicator"))
       .def_property_readonly("iteration_number", &radler::Radler::IterationNumber)
-      .def_property_readonly("component_list", &radler::Radler::GetComponentList);
+      .def_property_readonly("component_list", &radler::Radler::GetComponentList)
+      // what ComponentList::WriteSources takes from MaxScaleCountAlgorithm():
+      // its fitter (a copy) and the scale sizes ([0] unless multiscale)
+      .def_property_readonly("spectral_fitter",
+                             [](const radler::Radler& self) {
+                               return schaapcommon::fitters::SpectralFitter(
+                                   self.MaxScaleCountAlgorithm().Fitter());
+                             })
+      .def_property_readonly("scale_sizes", [](const radler::Radler& self) {
+        std::vector<double> sizes(1, 0.0);
+        if (const auto* multiscale = dynamic_cast<const radler::algorithms::MultiScaleAlgorithm*>(
+                &self.MaxScaleCountAlgorithm())) {
+          sizes.resize(multiscale->ScaleCount());
+          for (size_t i = 0; i != sizes.size(); ++i) sizes[i] = multiscale->ScaleSize(i);
+        }
+        return sizes;
+      });
 }
 
 void InitComponentList(py::module& m) {  // python/pycomponent_list.cc
@@ -475,7 +502,51 @@ void InitComponentList(py::module& m) {  // python/pycomponent_list.cc
         py::list out;
         for (const auto& p : self.GetPositions(s)) out.append(py::make_tuple(p.x, p.y));
         return out;
-      });
+      })
+      .def("write_sources", &radler::ComponentList::WriteSources, py::arg("radler"),
+           py::arg("filename"), py::arg("pixel_scale_x"), py::arg("pixel_scale_y"),
+           py::arg("phase_centre_ra"), py::arg("phase_centre_dec"), py::arg("l_shift") = 0.0,
+           py::arg("m_shift") = 0.0, py::call_guard<py::gil_scoped_release>())
+      .def("write",
+           [](const radler::ComponentList& self, const std::string& filename,
+              const schaapcommon::fitters::SpectralFitter& fitter,
+              const std::vector<double>& scale_sizes, long double pixel_scale_x,
+              long double pixel_scale_y, long double phase_centre_ra,
+              long double phase_centre_dec, long double l_shift, long double m_shift,
+              bool device) {
+             // ComponentList::Write with a fitter and scale sizes; `device`
+             // fits the terms in batches on the default device's session
+             // instead of with fitter.fit per component (the host path)
+             std::shared_ptr<radler::gpu::Session> session;
+             if (device)
+               session = radler::gpu::Session::ForDevice(radler::gpu::Session::DefaultDevice());
+             py::gil_scoped_release release;
+             self.Write(filename, fitter, scale_sizes, pixel_scale_x, pixel_scale_y,
+                        phase_centre_ra, phase_centre_dec, l_shift, m_shift, session.get());
+           },
+           py::arg("filename"), py::arg("fitter"), py::arg("scale_sizes"),
+           py::arg("pixel_scale_x"), py::arg("pixel_scale_y"), py::arg("phase_centre_ra"),
+           py::arg("phase_centre_dec"), py::arg("l_shift") = 0.0, py::arg("m_shift") = 0.0,
+           py::arg("device") = false)
+      .def("fit_terms",
+           [](const radler::ComponentList& self, size_t s,
+              const schaapcommon::fitters::SpectralFitter& fitter, bool device) {
+             // the terms write() gives the components of scale s:
+             // (component_count(s), terms per component)
+             if (s >= self.NScales()) throw std::out_of_range("Scale index out of range");
+             std::shared_ptr<radler::gpu::Session> session;
+             if (device)
+               session = radler::gpu::Session::ForDevice(radler::gpu::Session::DefaultDevice());
+             std::vector<float> terms;
+             {
+               py::gil_scoped_release release;
+               terms = self.FitTerms(s, fitter, session.get());
+             }
+             py::array_t<float> out({self.ComponentCount(s), self.TermCount(fitter)});
+             std::copy(terms.begin(), terms.end(), out.mutable_data());
+             return out;
+           },
+           py::arg("scale_index"), py::arg("fitter"), py::arg("device") = false);
 }
 
 py::dict ResultDict(const radler::algorithms::ParallelDeconvolutionResult& r,
