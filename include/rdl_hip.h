@@ -711,7 +711,7 @@ int rdl_conv_columns_layout(rdl_conv* c, const void* d_in, void* d_out,
                             const uint8_t* d_row_mask, int in_layout,
                             int kernel_layout, int out_layout);
 /* Which passes of this plan use the compile-time-planned kernels
- * (csrc/hip/fft_fast.hip): a bitmask of the two flags. */
+ * (csrc/hip/fft_fast*.hip): a bitmask of the two flags. */
 #define RDL_CONV_FAST_COLUMNS 1
 #define RDL_CONV_FAST_ROWS 2
 /* float planes with four-step column plans: every spectrum of this plan is

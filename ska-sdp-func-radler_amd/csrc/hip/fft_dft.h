@@ -1,5 +1,5 @@
 // Complex arithmetic and register-resident radix-R DFT butterflies shared by
-// the LDS-resident FFT engines (lds_fft.hip: runtime plans; fft_fast.hip:
+// the LDS-resident FFT engines (lds_fft.hip: runtime plans; fft_fast*.hip:
 // compile-time plans). Forward transforms, e^{-2 pi i jk/R}.
 #pragma once
 

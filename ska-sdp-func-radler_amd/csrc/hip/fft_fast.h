@@ -1,4 +1,4 @@
-// Compile-time-planned FFT kernels (fft_fast.hip): plan lookup and launches
+// Compile-time-planned FFT kernels (fft_fast*.hip): plan lookup and launches
 // used by the LDS engine's host code (lds_fft.hip) for the sizes they cover.
 #pragma once
 
@@ -45,11 +45,9 @@ struct FastRows {
   uint32_t n;  // full row length (2 x the half-length transform)
   bool f64;
   uint32_t threads;
-  const void* inverse;
-  const void* forward;
+  const void* inverse;  // float: LDS double twiddles, persistent (ff::RowsInverse, LT);
+  const void* forward;  //   double: the global pass tables
   RadixList radix;  // of the half-length transform
-  const void* inverse_lt;  // float: LDS double twiddles, persistent (else nullptr)
-  const void* forward_lt;
   const void* inverse_dma;  // float: ff::RowsInverseDma (else nullptr)
   size_t inverse_dma_lds;   // its dynamic LDS bytes
   const void* forward_dma;  // float: ff::RowsForwardDma (else nullptr)
@@ -123,8 +121,8 @@ struct RowPeak {
 /* spectrum rows oy .. oy+img_h-1 -> the img_w x img_h window at (ox, oy);
  * with `peak`, *n_partials = the peak partials written (one per row, or one
  * per workgroup for the LDS-DMA kernel) */
-/* twd: MakeTwiddleBase(n) for the float plans' LDS-twiddle kernels (NULL:
- * the global pass tables) */
+/* twd: MakeTwiddleBase(n), read by a float plan's kernels in place of tw and
+ * ptw (RDL_ERR_ARG without it); a double plan reads tw and ptw only */
 int FastRowsInverseLaunch(rdl_session* s, const FastRows* p, const void* spec, float* out,
                           const void* tw, const void* ptw, uint32_t height, uint32_t img_w, uint32_t img_h,
                           uint32_t ox, uint32_t oy, int subtract, int tiled = 0,
@@ -140,8 +138,8 @@ int FastRowsForwardLaunch(rdl_session* s, const FastRows* p, const float* in, vo
 int MakeTwiddleBase(uint32_t base, void** out, hipStream_t stream);
 /* float64 convolution columns (mode 1: forward, x K x s, inverse; row-major
  * input and output) with LDS twiddles and a register-resident K multiply
- * (ff::ColumnsConvD); nullptr where no plan exists or RDL_FFT_CONVD=0. tw:
- * the plan's length-n table W_n^k. */
+ * (ff::ColumnsConvD); nullptr where no plan exists. tw: the plan's length-n
+ * table W_n^k. */
 const FastColumns* FindConvColumnsD(uint32_t n);
 int ConvColumnsDLaunch(rdl_session* s, const FastColumns* p, const void* in, void* out,
                        const void* kern, const void* tw, uint32_t n_cols, int kern_cm,

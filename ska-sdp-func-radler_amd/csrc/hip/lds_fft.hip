@@ -515,7 +515,7 @@ struct rdl_conv {
   void* scratch_lane[2] = {nullptr, nullptr};
   void* scratch = nullptr;  // the current lane's (set by EnsureSplitScratch)
   size_t scratch_bytes[2] = {0, 0};
-  // compile-time-planned kernels (fft_fast.hip) where the size has a plan
+  // compile-time-planned kernels (fft_fast*.hip) where the size has a plan
   const rdl::FastColumns* fast_cols = nullptr;
   const rdl::FastColumns* conv_cols = nullptr;  // float64 mode-1 columns (ColumnsConvD)
   const rdl::FastRows* fast_rows = nullptr;
@@ -910,9 +910,11 @@ int rdl_conv_create_ex(rdl_session* s, uint32_t width, uint32_t height, int f64,
       c->steps = rdl::FindFastSteps(height);
       c->tiled = c->steps != nullptr;
     }
-    if (c->fast_rows)
+    // the row kernels' pass twiddles: double plans read the global pass
+    // table, float plans compute theirs from the two-level base in LDS
+    if (c->fast_rows && c->f64)
       RDL_TRY(rdl::MakePassTable(width / 2, c->fast_rows->radix, c->f64, &c->ptw_row, c->s->stream));
-    if (c->fast_rows && c->fast_rows->inverse_lt)
+    if (c->fast_rows && !c->f64)
       RDL_TRY(rdl::MakeTwiddleBase(width, &c->twd_row, c->s->stream));
     if (c->fast_cols)
       RDL_TRY(rdl::MakePassTable(height, c->fast_cols->radix, c->f64, &c->ptw_col, c->s->stream));

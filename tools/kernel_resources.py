@@ -1,7 +1,7 @@
 """Per-kernel register / occupancy / LDS summary of one HIP source, from
 hipcc -Rpass-analysis=kernel-resource-usage (compile only, no GPU).
 
-    python tools/kernel_resources.py ska-sdp-func-radler_amd/csrc/hip/fft_fast.hip [filter]
+    python tools/kernel_resources.py ska-sdp-func-radler_amd/csrc/hip/fft_fast_rows.hip [filter]
 """
 import os
 import re
