@@ -152,8 +152,10 @@ int rdl_find_peak_enqueue(rdl_session* s, const float* d_image, uint32_t width,
                           const uint8_t* d_mask, int avx_semantics, uint32_t slot);
 int rdl_find_peak_collect(rdl_session* s, uint32_t n, rdl_peak* out);
 
-/* Sum of squares in double (ThreadedDeconvolutionTools::RMS,
- * cpp/algorithms/threaded_deconvolution_tools.h:40-44; logging only). */
+/* *out = float(sqrt(sum v^2 / n)), the sum of squares accumulated in double
+ * (ThreadedDeconvolutionTools::RMS,
+ * cpp/algorithms/threaded_deconvolution_tools.h:40-44; logging only).
+ * n == 0 is RDL_ERR_ARG. */
 int rdl_rms(rdl_session* s, const float* d_image, size_t n, float* out);
 
 /* --------------------------------------------------------- PSF subtraction */
@@ -242,13 +244,17 @@ int rdl_iuwt_apply_mask(rdl_session* s, float* d_coeffs, const uint8_t* d_mask,
                         uint32_t width, uint32_t height, uint32_t n_scales);
 /* DotProduct (iuwt_deconvolution_algorithm.cc:169-174) with a double sum. */
 int rdl_dot(rdl_session* s, const float* d_a, const float* d_b, size_t n, double* out);
-/* Snr's two sums over the coefficient planes (:308-321), double:
- * model_sum = sum m^2, noise_sum = sum (m - n)^2 (n = d_noisy, m = d_model). */
+/* Snr's two sums over the coefficient planes (:308-321), accumulated in
+ * double: model_sum = sum m^2, noise_sum = sum d^2 with d = float(m - n), the
+ * difference rounded to float before it is widened, as the reference's
+ * `float d = m[i] - n[i]` (n = d_noisy, m = d_model). n == 0 gives zeros. */
 int rdl_iuwt_snr_sums(rdl_session* s, const float* d_noisy, const float* d_model, size_t n,
                       double* model_sum, double* noise_sum);
 /* BoundingBox's scans (:180-214): with m = max |v| of the image, h_first[y]
  * and h_last[y] are the first and last x of row y with |v| > m * 0.01
- * (double compare), -1 for rows without any. */
+ * (double compare), -1 for rows without any. An image without pixels
+ * (width * height == 0) launches nothing and returns RDL_OK with every one of
+ * the `height` rows at -1. */
 int rdl_bbox_rows(rdl_session* s, const float* d_image, uint32_t width, uint32_t height,
                   int32_t* h_first, int32_t* h_last);
 /* float <-> double planes (to_f64: float src -> double dst). */
@@ -563,10 +569,13 @@ int rdl_subminor_model_f64(rdl_subminor* h, uint32_t image_index,
                            uint32_t ox, uint32_t oy);
 /* Mode 0 of rdl_subminor_model (at offset 0,0) restricted to the rows that
  * hold a non-zero model value: the rows y of d_dest marked d_rows[y + oy]
- * (rdl_subminor_model_rows' mask) are zeroed and every component is stored;
- * other rows keep their contents, which the masked correction transform
- * (rdl_conv_rows_forward_masked) never reads. Replaces a full-plane zero fill
- * per outer iteration. */
+ * (rdl_subminor_model_rows' mask) are zeroed, then the model value of every
+ * selected pixel is stored, zero values included. So a marked row equals mode
+ * 0's row; in an unmarked row the selected pixels (all of value 0 there) are
+ * overwritten with 0.0 and every other pixel keeps its contents. The masked
+ * correction transform (rdl_conv_rows_forward_masked) never reads unmarked
+ * rows. Replaces a full-plane zero fill per outer iteration. With an empty
+ * selection nothing is written. */
 int rdl_subminor_model_masked(rdl_subminor* h, uint32_t image_index, float* d_dest,
                               uint32_t dest_w, uint32_t dest_h, const uint8_t* d_rows,
                               uint32_t oy);
@@ -795,7 +804,8 @@ int rdl_trim(rdl_session* s, float* d_dest, uint32_t width, uint32_t height,
  * Lets the multiscale transforms (multiscale_transforms.cc:9-21, circular at
  * W x H) run at an FFT-friendly size: a kernel of radius r <= shift convolved
  * with this plane and cropped at (shift_x, shift_y) is the circular
- * convolution at W x H, whatever prime factors W and H have. */
+ * convolution at W x H, whatever prime factors W and H have. An empty
+ * destination (pw * ph == 0) launches nothing and returns RDL_OK. */
 int rdl_periodic_extend(rdl_session* s, float* d_dest, uint32_t pw, uint32_t ph,
                         const float* d_src, uint32_t width, uint32_t height,
                         uint32_t shift_x, uint32_t shift_y);

@@ -476,6 +476,7 @@ int rdl_periodic_extend(rdl_session* s, float* d_dest, uint32_t pw, uint32_t ph,
                         uint32_t shift_x, uint32_t shift_y) {
   RDL_ARG_CHECK(s && d_dest && d_src, "NULL argument");
   RDL_ARG_CHECK(width > 0 && height > 0 && ph < 65536, "bad plane size");
+  if (pw == 0 || ph == 0) return RDL_OK;  // empty destination: nothing to launch
   rdl::ScopedTiming t(s, "extend", double(pw) * ph * 8.0);
   const dim3 grid((pw + 255) / 256, ph);
   rdl::PeriodicExtendKernel<<<grid, 256, 0, s->stream>>>(d_dest, pw, ph, d_src, width,

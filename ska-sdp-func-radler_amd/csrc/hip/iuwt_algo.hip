@@ -349,6 +349,10 @@ int rdl_bbox_rows(rdl_session* s, const float* d_image, uint32_t width, uint32_t
                   int32_t* h_first, int32_t* h_last) {
   RDL_ARG_CHECK(s && d_image && h_first && h_last, "NULL argument");
   const size_t n = size_t(width) * height;
+  if (n == 0) {  // no pixel: nothing to launch, and no row holds one
+    for (uint32_t y = 0; y < height; ++y) h_first[y] = h_last[y] = -1;
+    return RDL_OK;
+  }
   const uint32_t blocks = std::min<uint32_t>(1024, rdl::DivUp(n, 256));
   const size_t rows_bytes = size_t(height) * sizeof(int32_t);
   RDL_TRY(s->EnsureScratch(s->partials, blocks * sizeof(float) + 2 * rows_bytes + 64));

@@ -44,3 +44,46 @@ def test_struct_layouts_match_header():
     assert C.sizeof(Integration) == 4 * 6 + 4 * 64 + 4
     assert C.sizeof(HogbomParams) % 8 == 0
     assert C.sizeof(SubminorParams) % 8 == 0
+
+
+# Entry points no test calls directly, each with the reason. Only runtime
+# plumbing without a numerical contract, the multi-rank calls, and passes that
+# run inside a tested entry point belong here: anything else gets a test.
+NOT_CALLED_DIRECTLY = {
+    "rdl_device_count": "runtime query, no numerical contract",
+    "rdl_host_alloc": "pinned host allocation, no numerical contract",
+    "rdl_host_free": "pinned host allocation, no numerical contract",
+    "rdl_session_bind": "makes the device current for a worker thread, no numerical contract",
+    "rdl_memcpy_peer": "copy between two GPUs, no numerical contract",
+    "rdl_timing_enable": "per-session timing switch, no numerical contract",
+    "rdl_timing_get": "per-session timing read-out, no numerical contract",
+    "rdl_timing_reset": "per-session timing reset, no numerical contract",
+    "rdl_comm_id_size": "needs several ranks: tests/test_distributed.py through the host library",
+    "rdl_comm_get_unique_id": "needs several ranks: tests/test_distributed.py through the host library",
+    "rdl_comm_init": "needs several ranks: tests/test_distributed.py through the host library",
+    "rdl_comm_destroy": "needs several ranks: tests/test_distributed.py through the host library",
+    "rdl_comm_allreduce_max": "needs several ranks: tests/test_distributed.py through the host library",
+    "rdl_comm_allreduce_sum_u64": "needs several ranks: tests/test_distributed.py through the host library",
+    "rdl_comm_allreduce_max_n": "needs several ranks: tests/test_distributed.py through the host library",
+    "rdl_comm_broadcast": "needs several ranks: tests/test_distributed.py through the host library",
+    "rdl_comm_rank": "needs several ranks: tests/test_distributed.py through the host library",
+    "rdl_conv_columns_window": "the column pass of rdl_conv_convolve_subtract, which is tested",
+    "rdl_fft64_inverse": "the inverse transform of rdl_fft64_convolve, which is tested",
+}
+
+
+def test_every_entry_point_is_called_by_a_test_or_listed_with_a_reason():
+    import glob
+    import re
+    tests = os.path.dirname(os.path.abspath(__file__))
+    text = "".join(open(f).read() for f in sorted(glob.glob(os.path.join(tests, "*.py"))))
+    declared = declared_symbols()
+    called = {s for s in declared if re.search(r"\b" + s + r"\s*\(", text)}
+    uncovered = [s for s in declared if s not in called and s not in NOT_CALLED_DIRECTLY]
+    assert not uncovered, f"no test calls these entry points: {uncovered}"
+    stale = sorted(s for s in NOT_CALLED_DIRECTLY if s in called or s not in declared)
+    assert not stale, f"listed as not called, but called or no longer declared: {stale}"
+    allowed = re.compile(r"rdl_(device_count|host_alloc|host_free|session_bind|session_lane|"
+                         r"session_join|memcpy_peer|timing_(enable|get|reset)|comm_\w+|"
+                         r"conv_columns_layout|conv_columns_window|fft64_inverse)$")
+    assert all(allowed.match(s) and reason for s, reason in NOT_CALLED_DIRECTLY.items())

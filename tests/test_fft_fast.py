@@ -290,3 +290,69 @@ def test_rows_inverse_fused_peak_matches_find_peak(sess, w, h, hb, vb, neg, mask
     for x in (di, spec, work, kspec, dk, out_a, out_b) + ((dmask,) if masked else ()):
         x.free()
     sess.rdl.rdl_conv_destroy(c)
+
+
+RDL_CONV_FAST_COLUMNS = 1  # rdl_hip.h
+
+
+@pytest.mark.parametrize("w,h,f64", [(1250, 1176, True),    # compile-time columns: every layout
+                                     (1536, 2048, False),   # tiled: the layouts do not apply
+                                     (96, 60, True)])       # runtime plan: row-major input only
+def test_columns_layout_matches_numpy(sess, w, h, f64):
+    """rdl_conv_columns_layout as the host's Fft calls it: a mode-0 spectrum
+    written column-major, the in-place convolution (mode 1) with the kernel in
+    either layout, and the shared-spectrum convolution (mode 2) with input and
+    kernel both row-major or both column-major. float64 |err| <= half a float
+    ulp + 1e-12 * scale, float32 |err| <= 2e-6 * scale, as above."""
+    rng = np.random.default_rng(5 * w + h)
+    img = rng.standard_normal((h, w)).astype(np.float32)
+    ker = np.zeros((h, w), np.float32)
+    ker[:7, :9] = rng.standard_normal((7, 9))
+    ker = np.roll(ker, (-3, -4), axis=(0, 1)).copy()
+    ref = np.fft.irfft2(np.fft.rfft2(img.astype(np.float64)) *
+                        np.fft.rfft2(ker.astype(np.float64)), s=(h, w))
+    c = conv(sess, w, h, f64)
+    fast = bool(sess.rdl.lib.rdl_conv_fast(c) & RDL_CONV_FAST_COLUMNS) or tiled(sess, c)
+    assert fast or w == 96
+    cdt = np.complex128 if f64 else np.complex64
+    dk, di = sess.array(ker), sess.array(img)
+    kspec, kspec_cm, sspec, sspec_cm, work = (spectrum_array(sess, c, w, h, cdt) for _ in range(5))
+    out = sess.array(shape=(h, w))
+    one = C.c_double(1.0)
+    for plane, rm, cm in ((dk, kspec, kspec_cm), (di, sspec, sspec_cm)):
+        sess.rdl.rdl_conv_forward(c, plane.vp, rm.vp)
+        sess.rdl.rdl_conv_rows_forward(c, plane.vp, w, h, 0, 0, work.vp)
+        sess.rdl.rdl_conv_columns_layout(c, work.vp, cm.vp, None, 0, one, None,
+                                         RDL_CONV_ROW_MAJOR, RDL_CONV_ROW_MAJOR, RDL_CONV_COL_MAJOR)
+        if tiled(sess, c):
+            assert np.array_equal(cm.get(), rm.get())
+        else:
+            t = cm.get()[:(w // 2 + 1) * h].reshape(w // 2 + 1, h)
+            assert np.abs(t.T - natural(sess, c, rm.get(), w, h)).max() == 0.0
+    norm = 1.0 / (w * h) if f64 else float(np.float32(1.0 / (w * h)))
+
+    def close(got):
+        scale = np.abs(ref).max() * np.sqrt(np.log2(w * h))
+        if f64:
+            half_ulp = 0.5 * np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
+            return np.all(np.abs(got - ref) <= half_ulp + 1e-12 * scale)
+        return np.abs(got - ref).max() <= 2e-6 * scale
+    for kern, image, layout in ((kspec, sspec, RDL_CONV_ROW_MAJOR),
+                                (kspec_cm, sspec_cm, RDL_CONV_COL_MAJOR)):
+        sess.rdl.rdl_conv_rows_forward(c, di.vp, w, h, 0, 0, work.vp)
+        sess.rdl.rdl_conv_columns_layout(c, work.vp, work.vp, kern.vp, 1, C.c_double(norm), None,
+                                         RDL_CONV_ROW_MAJOR, layout, RDL_CONV_ROW_MAJOR)
+        sess.rdl.rdl_conv_rows_inverse(c, work.vp, out.vp, w, h, 0, 0, 0)
+        assert close(out.get())
+        args = (c, image.vp, work.vp, kern.vp, 2, C.c_double(norm), None, layout, layout,
+                RDL_CONV_ROW_MAJOR)
+        if layout == RDL_CONV_COL_MAJOR and not fast:
+            with pytest.raises(RuntimeError, match="rc=5:"):   # RDL_ERR_UNSUPPORTED
+                sess.rdl.rdl_conv_columns_layout(*args)
+            continue
+        sess.rdl.rdl_conv_columns_layout(*args)
+        sess.rdl.rdl_conv_rows_inverse(c, work.vp, out.vp, w, h, 0, 0, 0)
+        assert close(out.get())
+    for x in (dk, di, kspec, kspec_cm, sspec, sspec_cm, work, out):
+        x.free()
+    sess.rdl.rdl_conv_destroy(c)
