@@ -898,6 +898,64 @@ int rdl_bits_differ_enqueue(rdl_session* s, const void* d_a, const void* d_b, si
                             int first);
 int rdl_bits_differ_collect(rdl_session* s, int* differ);
 
+/* ---------------------------------------------------- adaptive scale pixel */
+/* The three device primitives of AspAlgorithm (cpp/algorithms/
+ * asp_algorithm.cc). They share one elliptical Gaussian,
+ *   g(x, y) = exp(-1/2 (u^2 / sigma_maj^2 + v^2 / sigma_min^2)),
+ *   u =  (x - x0) cos(pa) + (y - y0) sin(pa),
+ *   v = -(x - x0) sin(pa) + (y - y0) cos(pa),
+ *   sigma = FWHM / (2 sqrt(2 ln 2)),
+ * with x the column and y the row index of a pixel, FWHMs in pixels and the
+ * position angle pa in radians: the angle of the major axis from the +x axis
+ * towards the +y axis. The fitter, the renderer and the weights all use this
+ * one convention, so the reference's `position_angle *= -1` between its
+ * fitter and its renderer (asp_algorithm.cc:291-292) has no counterpart. g is
+ * evaluated in double. The reference takes these from schaapcommon
+ * (fitters/gaussianfitter.h, math/drawgaussian.h), whose source is not part
+ * of the reference snapshot: the contracts below are stated from its
+ * interface as asp_algorithm.cc uses it, not from its source. */
+
+/* The normal-equation sums of a least-squares fit of A g to a box of a float
+ * image (schaapcommon::fitters::Fit2DGaussianFull / Fit2DGaussianCentred,
+ * asp_algorithm.cc:72-73, 267-269, one Levenberg-Marquardt step's device
+ * work). params (host) = {A, x0, y0, FWHM_maj, FWHM_min, pa}; the box
+ * (box_x, box_y, box_w, box_h) lies inside the image. With the residual
+ * r = image - A g and J the 6 columns d(A g)/d params (analytic), out (host)
+ * receives RDL_GAUSSIAN_FIT_SUMS doubles: the upper triangle of J^T J row by
+ * row (21: (0,0) (0,1) .. (0,5) (1,1) .. (5,5)), J^T r (6), sum r^2 (1).
+ * Deterministic: double accumulation in a fixed order (per thread, wave64
+ * butterfly, the block's waves, one slab row per block, the rows), no
+ * floating-point atomics, a grid that depends on the box size only; the same
+ * call gives the same 28 bit patterns on every run. One 224-byte read-back. */
+#define RDL_GAUSSIAN_FIT_SUMS 28
+int rdl_gaussian_fit_sums(rdl_session* s, const float* d_image, uint32_t width,
+                          uint32_t height, uint32_t box_x, uint32_t box_y, uint32_t box_w,
+                          uint32_t box_h, const double* params, double* out);
+/* d_plane += float(flux g / (2 pi sigma_maj sigma_min)): a Gaussian of unit
+ * integral times `flux`, centred on the sub-pixel position (x0, y0)
+ * (schaapcommon::math::DrawGaussianToXy as asp_algorithm.cc:296 needs it, a
+ * kernel of integral 1, and :337-339 reads consistently with). Evaluated in
+ * double, rounded once, added in float. Only the pixels within
+ * ceil(6 sigma_maj) of the centre along both axes, clipped to the plane, are
+ * touched: beyond 6 sigma g < exp(-18) = 1.5e-8, under half a float ulp of
+ * the peak. */
+int rdl_draw_gaussian(rdl_session* s, float* d_plane, uint32_t width, uint32_t height,
+                      double x0, double y0, double fwhm_major, double fwhm_minor, double pa,
+                      double flux);
+/* out[i] (host, double) = sum over (dx, dy) of w(dx, dy) *
+ * plane_i[centre_y[i] + dy][centre_x[i] + dx], plane_i = d_planes +
+ * i * plane_stride (floats), w the unit-integral Gaussian of
+ * rdl_draw_gaussian centred on the pixel, over the same 6 sigma box; pixels
+ * outside the plane count as zero. One launch for all n_planes
+ * (<= RDL_GAUSSIAN_MAX_PLANES) planes, reduced as rdl_gaussian_fit_sums.
+ * Replaces the PsfCount() + Size() whole-image FFT convolutions that
+ * asp_algorithm.cc:303-327 runs to read one pixel of each. */
+#define RDL_GAUSSIAN_MAX_PLANES 128
+int rdl_gaussian_weighted_values(rdl_session* s, const float* d_planes, size_t plane_stride,
+                                 uint32_t n_planes, uint32_t width, uint32_t height,
+                                 const uint32_t* centre_x, const uint32_t* centre_y,
+                                 double fwhm_major, double fwhm_minor, double pa, double* out);
+
 #ifdef __cplusplus
 }
 #endif

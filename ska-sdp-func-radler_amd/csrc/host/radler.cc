@@ -7,6 +7,7 @@
 #include <sstream>
 #include <stdexcept>
 
+#include "asp_algorithm.h"
 #include "device.h"
 #include "fits_image.h"
 #include "generic_clean.h"
@@ -314,8 +315,10 @@ void Radler::InitializeDeconvolutionAlgorithm(
     case AlgorithmType::kIuwt:
       algorithm = std::make_unique<algorithms::IuwtDeconvolution>();
       break;
-    case AlgorithmType::kAdaptiveScalePixel:
-      Unsupported("The adaptive scale pixel algorithm");
+    case AlgorithmType::kAdaptiveScalePixel:  // :355-358
+      algorithm = std::make_unique<algorithms::AspAlgorithm>(
+          settings_.multiscale, beam_size_, pixel_scale_x_, pixel_scale_y_);
+      break;
     case AlgorithmType::kMoreSane:
       Unsupported("MoreSane");
     case AlgorithmType::kPython:

@@ -14,6 +14,7 @@
 #include "device_run.h"
 #include "fits_image.h"
 #include "dijkstra_splitter.h"
+#include "gaussian_fit.h"
 #include "image_accessors.h"
 #include "logger.h"
 #include "multiscale_algorithm.h"
@@ -47,6 +48,9 @@ void InitSettings(py::module& m) {  // python/pysettings.cc
       .value("generic_clean", radler::AlgorithmType::kGenericClean)
       .value("multiscale", radler::AlgorithmType::kMultiscale)
       .value("iuwt", radler::AlgorithmType::kIuwt)
+      // absent from the reference's binding (python/pysettings.cc); here the
+      // only way a Python caller selects the algorithm
+      .value("adaptive_scale_pixel", radler::AlgorithmType::kAdaptiveScalePixel)
       .value("more_sane", radler::AlgorithmType::kMoreSane)
       .value("python", radler::AlgorithmType::kPython);
   py::enum_<radler::OptimizationAlgorithm>(m, "OptimizationAlgorithm")
@@ -1111,6 +1115,59 @@ void InitGpu(py::module& m) {
       });
 }
 
+void InitFitters(py::module& m) {
+  // schaapcommon::fitters as AspAlgorithm uses it (csrc/host/gaussian_fit.h)
+  py::module f = m.def_submodule("fitters", "Elliptical Gaussian fitting (gaussian_fit.h)");
+  f.def(
+      "fit_2d_gaussian_full",
+      [](FloatArray image, double amplitude, double x, double y, double major, double minor,
+         double pa) {
+        if (image.ndim() != 2) throw std::runtime_error("expected a 2-D image");
+        const size_t h = image.shape(0), w = image.shape(1), n = w * h;
+        std::shared_ptr<radler::gpu::Session> session =
+            radler::gpu::Session::ForDevice(radler::gpu::Session::DefaultDevice());
+        radler::gpu::Session& s = *session;
+        radler::gpu::Buffer d(s, n * sizeof(float));
+        s.H2D(d.Ptr(), image.data(), n * sizeof(float));
+        {
+          py::gil_scoped_release release;
+          schaapcommon::fitters::Fit2DGaussianFull(s, d.F(), w, h, amplitude, x, y, major, minor,
+                                                   pa);
+        }
+        return py::make_tuple(amplitude, x, y, major, minor, pa);
+      },
+      py::arg("image"), py::arg("amplitude"), py::arg("x"), py::arg("y"), py::arg("major"),
+      py::arg("minor"), py::arg("pa"));
+  f.def(
+      "fit_2d_gaussian_centred",
+      [](FloatArray image, double beam_estimate) {
+        if (image.ndim() != 2) throw std::runtime_error("expected a 2-D image");
+        const size_t h = image.shape(0), w = image.shape(1), n = w * h;
+        std::shared_ptr<radler::gpu::Session> session =
+            radler::gpu::Session::ForDevice(radler::gpu::Session::DefaultDevice());
+        radler::gpu::Session& s = *session;
+        radler::gpu::Buffer d(s, n * sizeof(float));
+        s.H2D(d.Ptr(), image.data(), n * sizeof(float));
+        schaapcommon::math::Ellipse e;
+        {
+          py::gil_scoped_release release;
+          e = schaapcommon::fitters::Fit2DGaussianCentred(s, d.F(), w, h, beam_estimate);
+        }
+        return py::make_tuple(e.major, e.minor, e.position_angle);
+      },
+      py::arg("image"), py::arg("beam_estimate"));
+  f.def(
+      "deconvolve_gaussian",
+      [](double major, double minor, double pa, double psf_major, double psf_minor,
+         double psf_pa) {
+        const schaapcommon::math::Ellipse e = schaapcommon::fitters::DeconvolveGaussian(
+            {major, minor, pa}, {psf_major, psf_minor, psf_pa});
+        return py::make_tuple(e.major, e.minor, e.position_angle);
+      },
+      py::arg("major"), py::arg("minor"), py::arg("pa"), py::arg("psf_major"),
+      py::arg("psf_minor"), py::arg("psf_pa"));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(radler, m) {  // python/pywrappers.cc
@@ -1124,4 +1181,5 @@ PYBIND11_MODULE(radler, m) {  // python/pywrappers.cc
   InitGpu(m);
   InitTiling(m);
   InitDistributed(m);
+  InitFitters(m);
 }
