@@ -414,6 +414,40 @@ int rdl_component_terms(rdl_session* s, uint32_t mode, uint32_t n_channels,
                         const uint32_t* h_y, const float* d_values, size_t value_stride,
                         size_t n_components, float* d_terms, size_t term_stride);
 
+/* ------------------------------------- component list: rendering to planes */
+/* The inverse of rdl_component_terms: the flux of n_components components at
+ * n_out outputs, written as delta planes, one lane per component. d_in has
+ * the layout of d_terms / d_values above (row k of component i at
+ * d_in + k * in_stride + i, n_in rows). The n_out planes (width x height,
+ * plane_stride floats apart) are zeroed; plane g at (h_x[i], h_y[i]) then
+ * receives component i's flux at output g. By mode:
+ *   RDL_TERMS_POLYNOMIAL  the rows are terms and h_out[g] = nu_g / nu_ref - 1:
+ *                         x = float(h_out[g]); value = t0; power *= x;
+ *                         value += power * t_k, all in float and uncontracted:
+ *                         SpectralFitter::Evaluate's loop, bit for bit
+ *                         (n_in <= RDL_MAX_IMAGES);
+ *   RDL_TERMS_LOGPOLY,    the rows are terms and h_out[g] = log10(nu_g /
+ *   RDL_TERMS_FORCED      nu_ref): rdl::lp::Evaluate(terms, n_in, h_out[g])
+ *                         of csrc/hip/logpoly.h, the host fitter's function (a
+ *                         forced fit evaluates the same way;
+ *                         n_in <= RDL_LOGPOLY_MAX_TERMS);
+ *   RDL_RENDER_VALUES     the rows are values: plane g receives row g
+ *                         unchanged (h_out == NULL, n_out == n_in).
+ * 1 <= n_in, n_out <= RDL_MAX_IMAGES. The positions are host arrays: every one
+ * is checked against width x height, and the list against repeated positions,
+ * before anything is launched (RDL_ERR_ARG). Distinct positions make the
+ * plain stores deterministic. Every argument error is returned before the
+ * first device call. n_components == 0 only zeroes the planes (d_in, h_x and
+ * h_y may then be NULL). One launch covers RDL_RENDER_LANES components per
+ * pass of its grid-stride loop. */
+#define RDL_RENDER_VALUES 3u
+#define RDL_RENDER_LANES (256u * 1024u)
+int rdl_render_components(rdl_session* s, uint32_t mode, uint32_t n_in,
+                          const float* d_in, size_t in_stride, size_t n_components,
+                          const uint32_t* h_x, const uint32_t* h_y, uint32_t width,
+                          uint32_t height, const double* h_out, uint32_t n_out,
+                          float* d_planes, size_t plane_stride);
+
 /* ---------------------------------------------------------------- Högbom */
 typedef struct {
   uint32_t width, height;
@@ -765,6 +799,13 @@ int rdl_conv_scale_finish(rdl_conv* c, const void* d_in, void* d_out);
 /* dst = a * b * scale, complex, n_complex elements. */
 int rdl_spectrum_multiply(rdl_session* s, void* d_dst, const void* d_a,
                           const void* d_b, size_t n_complex, float scale);
+/* acc += a * b * scale, complex float, n_complex elements: each product is
+ * formed as in rdl_spectrum_multiply and then added, uncontracted. Summing
+ * several scales' image x kernel spectra this way costs one inverse transform
+ * for the sum instead of one per scale (ComponentList::Render). d_acc may not
+ * overlap d_a or d_b. n_complex == 0 does nothing. */
+int rdl_spectrum_multiply_add(rdl_session* s, void* d_acc, const void* d_a,
+                              const void* d_b, size_t n_complex, float scale);
 /* Circular convolution of d_image (in place) with a kernel spectrum:
  * schaapcommon::math::Convolve contract (multiscale_transforms.cc:16-20,
  * subminor_loop.cc:210-211); normalised. d_work: spectrum-sized scratch. */

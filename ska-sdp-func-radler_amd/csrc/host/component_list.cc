@@ -256,21 +256,20 @@ std::unique_ptr<ComponentList::DeviceFit> ComponentList::MakeDeviceFit(
   return fit;
 }
 
-std::vector<float> ComponentList::FitTermsOnDevice(size_t scale_index, size_t n_terms,
-                                                   const DeviceFit& fit) const {
+void ComponentList::FitTermsIntoDevice(size_t scale_index, size_t n_terms, const DeviceFit& fit,
+                                       gpu::Buffer& d_terms) const {
   const ScaleList& list = list_per_scale_[scale_index];
   const size_t n = list.positions.size();
-  std::vector<float> terms(n * n_terms);
-  if (n == 0) return terms;
+  if (n == 0) return;
   // channel-major spectra in, term-major terms out
   gpu::Session& s = fit.session;
   s.Bind();
-  std::vector<float> staged(n * std::max(n_frequencies_, n_terms));
+  std::vector<float> staged(n * n_frequencies_);
   for (size_t i = 0; i != n; ++i)
     for (size_t f = 0; f != n_frequencies_; ++f)
       staged[f * n + i] = list.values[i * n_frequencies_ + f];
-  gpu::Buffer d_values(s, n * n_frequencies_ * sizeof(float)),
-      d_terms(s, n * n_terms * sizeof(float));
+  gpu::Buffer d_values(s, n * n_frequencies_ * sizeof(float));
+  d_terms.Resize(s, n * n_terms * sizeof(float));
   s.H2D(d_values.Ptr(), staged.data(), n * n_frequencies_ * sizeof(float));
   std::vector<uint32_t> xy;
   if (fit.mode == RDL_TERMS_FORCED) {
@@ -286,7 +285,18 @@ std::vector<float> ComponentList::FitTermsOnDevice(size_t scale_index, size_t n_
                                  xy.empty() ? nullptr : xy.data() + n, d_values.F(), n, n,
                                  d_terms.F(), n),
              "rdl_component_terms");
-  s.D2H(staged.data(), d_terms.Ptr(), n * n_terms * sizeof(float));
+  // d_values is released in stream order, after the fit that reads it
+}
+
+std::vector<float> ComponentList::FitTermsOnDevice(size_t scale_index, size_t n_terms,
+                                                   const DeviceFit& fit) const {
+  const size_t n = list_per_scale_[scale_index].positions.size();
+  std::vector<float> terms(n * n_terms);
+  if (n == 0) return terms;
+  gpu::Buffer d_terms;
+  FitTermsIntoDevice(scale_index, n_terms, fit, d_terms);
+  std::vector<float> staged(n * n_terms);
+  fit.session.D2H(staged.data(), d_terms.Ptr(), n * n_terms * sizeof(float));
   for (size_t i = 0; i != n; ++i)
     for (size_t t = 0; t != n_terms; ++t) terms[i * n_terms + t] = staged[t * n + i];
   return terms;
@@ -407,6 +417,177 @@ void ComponentList::WriteRows(const std::string& filename, const SpectralFitter&
     }
   }
   if (!file) throw std::runtime_error("ComponentList::Write: writing " + filename + " failed");
+}
+
+// ------------------------------------------------------------ model images
+void ComponentList::CheckRender(const SpectralFitter& fitter,
+                                const std::vector<double>& scale_sizes,
+                                const std::vector<double>& frequencies) const {
+  if (added_since_merge_ != 0)
+    throw std::runtime_error(
+        "ComponentList::Render called while there are yet unmerged components. "
+        "Run ComponentList::MergeDuplicates() first.");
+  if (scale_sizes.size() != NScales())
+    throw std::runtime_error("ComponentList::Render: " + std::to_string(scale_sizes.size()) +
+                             " scale sizes given for " + std::to_string(NScales()) + " scales");
+  for (double frequency : frequencies)
+    if (!(frequency > 0.0))
+      throw std::runtime_error("ComponentList::Render: a frequency is not positive");
+  // the list's own values need no fitter; terms come from the fit Write uses
+  const bool values = frequencies.empty();
+  const bool fitted = !values && n_frequencies_ > 1;
+  if (fitted) CheckWritable(fitter);
+  // a fitter that fits at all must be the list's, used or not
+  if (n_frequencies_ > 1 && fitter.Mode() != SpectralFittingMode::kNoFitting &&
+      fitter.Frequencies().size() != n_frequencies_)
+    throw std::runtime_error("ComponentList::Render: the components have " +
+                             std::to_string(n_frequencies_) +
+                             " frequencies, the spectral fitter has " +
+                             std::to_string(fitter.Frequencies().size()) + " channels");
+  const size_t n_out = values ? n_frequencies_ : frequencies.size();
+  if (n_out > RDL_MAX_IMAGES)
+    throw std::runtime_error("ComponentList::Render: more than " +
+                             std::to_string(RDL_MAX_IMAGES) + " planes asked for");
+}
+
+std::vector<aocommon::Image> ComponentList::Render(const Radler& radler,
+                                                   const std::vector<double>& frequencies) const {
+  const algorithms::DeconvolutionAlgorithm& algorithm = radler.MaxScaleCountAlgorithm();
+  std::vector<double> scale_sizes(NScales(), 0.0);
+  if (const auto* multiscale = dynamic_cast<const algorithms::MultiScaleAlgorithm*>(&algorithm))
+    for (size_t i = 0; i != NScales(); ++i) scale_sizes[i] = multiscale->ScaleSize(i);
+  return Render(algorithm.Fitter(), scale_sizes, radler.GetSettings().multiscale.shape,
+                frequencies, radler.DeviceSession(), algorithm.SpectrallyForcedImages().get());
+}
+
+std::vector<aocommon::Image> ComponentList::Render(const SpectralFitter& fitter,
+                                                   const std::vector<double>& scale_sizes,
+                                                   MultiscaleShape shape,
+                                                   const std::vector<double>& frequencies,
+                                                   gpu::Session& session) const {
+  return Render(fitter, scale_sizes, shape, frequencies, session, nullptr);
+}
+
+std::vector<aocommon::Image> ComponentList::Render(const SpectralFitter& fitter,
+                                                   const std::vector<double>& scale_sizes,
+                                                   MultiscaleShape shape,
+                                                   const std::vector<double>& frequencies,
+                                                   gpu::Session& session,
+                                                   const ForcedTermImages* images) const {
+  using algorithms::multiscale::MultiScaleTransforms;
+  CheckRender(fitter, scale_sizes, frequencies);
+  // the list's own values need no fitter; terms come from the fit Write uses
+  const bool values = frequencies.empty();
+  const bool fitted = !values && n_frequencies_ > 1;
+  const size_t n_out = values ? n_frequencies_ : frequencies.size();
+  std::vector<aocommon::Image> result;
+  if (n_out == 0 || width_ == 0 || height_ == 0) return result;
+
+  // what rdl_render_components evaluates the rows at (SpectralFitter::Evaluate)
+  uint32_t mode = RDL_RENDER_VALUES;
+  std::vector<double> at;
+  if (!values) {
+    const bool log_si = fitted && (fitter.Mode() == SpectralFittingMode::kLogPolynomial ||
+                                   fitter.Mode() == SpectralFittingMode::kForcedTerms);
+    // a single-frequency list: one term, its value, whatever the frequency
+    mode = log_si ? RDL_TERMS_LOGPOLY : RDL_TERMS_POLYNOMIAL;
+    for (double frequency : frequencies) {
+      const double ratio = fitted ? frequency / fitter.ReferenceFrequency() : 1.0;
+      at.push_back(log_si ? std::log10(ratio) : ratio - 1.0);
+    }
+  }
+  const size_t n_rows = values ? n_frequencies_ : TermCount(fitter);
+
+  gpu::Session& s = session;
+  s.Bind();
+  const size_t plane = width_ * height_;
+  MultiScaleTransforms transforms(s, width_, height_, shape);
+  float max_scale = 0.0f;
+  for (size_t scale = 0; scale != NScales(); ++scale)
+    if (ComponentCount(scale) != 0) max_scale = std::max(max_scale, float(scale_sizes[scale]));
+  if (max_scale != 0.0f) transforms.SetMaxScale(max_scale);
+  std::unique_ptr<DeviceFit> device_fit;
+  if (fitted) device_fit = MakeDeviceFit(fitter, s, images);
+
+  gpu::Buffer out(s, n_out * plane * sizeof(float)), delta(s, n_out * plane * sizeof(float));
+  gpu::Check(rdl_memset_zero(s.Handle(), out.Ptr(), n_out * plane * sizeof(float)),
+             "rdl_memset_zero");
+  // summed in the spectrum: one accumulator per plane, the transform of one
+  // delta plane at a time
+  gpu::Buffer accumulators, spectrum, rows;
+  size_t spectrum_bytes = 0;
+  bool accumulated = false;
+  std::vector<uint32_t> xy;
+  std::vector<float> staged;
+  for (size_t scale = 0; scale != NScales(); ++scale) {
+    const ScaleList& list = list_per_scale_[scale];
+    const size_t n = list.positions.size();
+    if (n == 0) continue;
+    xy.resize(2 * n);
+    for (size_t i = 0; i != n; ++i) {
+      xy[i] = uint32_t(list.positions[i].x);
+      xy[n + i] = uint32_t(list.positions[i].y);
+    }
+    if (fitted) {  // the terms stay on the device between the fit and the render
+      FitTermsIntoDevice(scale, n_rows, *device_fit, rows);
+    } else {
+      staged.resize(n * n_frequencies_);
+      for (size_t i = 0; i != n; ++i)
+        for (size_t f = 0; f != n_frequencies_; ++f)
+          staged[f * n + i] = list.values[i * n_frequencies_ + f];
+      rows.Resize(s, staged.size() * sizeof(float));
+      s.H2D(rows.Ptr(), staged.data(), staged.size() * sizeof(float));
+    }
+    gpu::Check(rdl_render_components(s.Handle(), mode, uint32_t(n_rows), rows.F(), n, n,
+                                     xy.data(), xy.data() + n, uint32_t(width_),
+                                     uint32_t(height_), values ? nullptr : at.data(),
+                                     uint32_t(n_out), delta.F(), plane),
+               "rdl_render_components");
+    const float size = float(scale_sizes[scale]);
+    if (size == 0.0f) {
+      gpu::Check(rdl_add(s.Handle(), out.F(), delta.F(), n_out * plane), "rdl_add");
+      continue;
+    }
+    const void* kernel = transforms.KernelSpectrum(size);
+    if (spectrum_bytes == 0) {
+      spectrum_bytes = transforms.SpectrumBytes();
+      accumulators.Resize(s, n_out * spectrum_bytes);
+      spectrum.Resize(s, spectrum_bytes);
+    }
+    // every element of the spectrum's storage, whatever its layout
+    const size_t n_complex = spectrum_bytes / (2 * sizeof(float));
+    for (size_t g = 0; g != n_out; ++g) {
+      void* accumulator = static_cast<char*>(accumulators.Ptr()) + g * spectrum_bytes;
+      transforms.Forward(delta.F() + g * plane, spectrum.Ptr());
+      if (!accumulated)
+        gpu::Check(rdl_spectrum_multiply(s.Handle(), accumulator, spectrum.Ptr(), kernel,
+                                         n_complex, 1.0f),
+                   "rdl_spectrum_multiply");
+      else
+        gpu::Check(rdl_spectrum_multiply_add(s.Handle(), accumulator, spectrum.Ptr(), kernel,
+                                             n_complex, 1.0f),
+                   "rdl_spectrum_multiply_add");
+    }
+    accumulated = true;
+  }
+  if (accumulated) {
+    // the one inverse: ConvolveSpectrum with the size-0 kernel, whose
+    // spectrum is 1 everywhere (a delta at the origin), so only the
+    // normalisation and the inverse transform act on the sum
+    for (size_t g = 0; g != n_out; ++g)
+      transforms.ConvolveSpectrum(static_cast<char*>(accumulators.Ptr()) + g * spectrum_bytes,
+                                  0.0f, spectrum.Ptr(), delta.F() + g * plane);
+    gpu::Check(rdl_add(s.Handle(), out.F(), delta.F(), n_out * plane), "rdl_add");
+  }
+  // the copies back wait for the device anyway; queued behind the pending
+  // kernels instead, the 8192^2 plane's copy took 17 ms, after this 5 ms
+  // (profiles/render_restore_timing.txt)
+  s.Sync();
+  for (size_t g = 0; g != n_out; ++g) {
+    result.emplace_back(width_, height_);
+    s.D2H(result.back().Data(), out.F() + g * plane, plane * sizeof(float));
+  }
+  return result;
 }
 
 void ComponentList::Clear() {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "aocommon_compat.h"
+#include "settings.h"
 
 #ifndef RADLER_AMD_USE_EXTERNAL_AOCOMMON
 namespace schaapcommon::fitters {
@@ -29,6 +30,7 @@ class DeconvolutionAlgorithm;
 class MultiScaleAlgorithm;
 }  // namespace algorithms
 namespace gpu {
+class Buffer;
 class Session;
 }
 
@@ -125,7 +127,42 @@ class ComponentList {
   /// (its value is its only term and nothing is fitted).
   size_t TermCount(const schaapcommon::fitters::SpectralFitter& fitter) const;
 
+  /// The list as model images on the device session: plane g = the sum over
+  /// the scales of (the scale's delta plane convolved with its shape kernel),
+  /// the convolution circular at Width() x Height() as MultiScaleAlgorithm
+  /// applies it to its own model (MultiScaleTransforms); a scale of size 0 is
+  /// added as it is. With `frequencies` empty the planes are the list's own
+  /// values, one per list frequency. Otherwise plane g is the list at
+  /// frequencies[g] (Hz): every component's terms, those Write prints
+  /// (FitTerms on the device, in any fitting mode), evaluated as
+  /// fitter.Evaluate does; a single-frequency list has its value as its only
+  /// term and gives the same plane at every frequency. The products of the
+  /// scales' spectra are summed and inverted once: a plane costs one forward
+  /// transform per non-zero scale that holds components, and one inverse.
+  /// Throws, before the first device call, on an unmerged list, a scale-size
+  /// count other than NScales(), a fitter whose channels are not the list's
+  /// and a frequency <= 0. The second form takes the fitter, the scale sizes,
+  /// the shape, the forced-term planes and the session of the Radler.
+  std::vector<aocommon::Image> Render(const schaapcommon::fitters::SpectralFitter& fitter,
+                                      const std::vector<double>& scale_sizes,
+                                      MultiscaleShape shape,
+                                      const std::vector<double>& frequencies,
+                                      gpu::Session& session) const;
+  std::vector<aocommon::Image> Render(const Radler& radler,
+                                      const std::vector<double>& frequencies = {}) const;
+  /// Render's checks of its arguments, on their own: throws what Render
+  /// would, and touches no device.
+  void CheckRender(const schaapcommon::fitters::SpectralFitter& fitter,
+                   const std::vector<double>& scale_sizes,
+                   const std::vector<double>& frequencies) const;
+
  private:
+  std::vector<aocommon::Image> Render(const schaapcommon::fitters::SpectralFitter& fitter,
+                                      const std::vector<double>& scale_sizes,
+                                      MultiscaleShape shape,
+                                      const std::vector<double>& frequencies,
+                                      gpu::Session& session,
+                                      const ForcedTermImages* images) const;
   struct ScaleList {
     std::vector<Position> positions;
     std::vector<float> values;
@@ -140,6 +177,10 @@ class ComponentList {
                                            const ForcedTermImages* images) const;
   std::vector<float> FitTermsOnDevice(size_t scale_index, size_t n_terms,
                                       const DeviceFit& fit) const;
+  /// The batched fit of a scale, its term-major result (n_terms rows of
+  /// ComponentCount(scale_index) floats) left in d_terms on the device.
+  void FitTermsIntoDevice(size_t scale_index, size_t n_terms, const DeviceFit& fit,
+                          gpu::Buffer& d_terms) const;
   std::vector<float> FitTermsOnHost(size_t scale_index, size_t n_terms,
                                     const schaapcommon::fitters::SpectralFitter& fitter) const;
   void WriteRows(const std::string& filename,

@@ -49,6 +49,9 @@ class Radler {
   // MI355X build only: the device session (bench / tests) and the
   // parallel-deconvolution object.
   gpu::Session& DeviceSession() const;
+  /// The settings this Radler was made with (ComponentList::Render takes the
+  /// multiscale shape from them).
+  const Settings& GetSettings() const { return settings_; }
   algorithms::ParallelDeconvolution& Parallel() const {
     return *parallel_deconvolution_;
   }

@@ -3,6 +3,8 @@
 #include <algorithm>
 #include <cmath>
 
+#include "restore.h"
+
 namespace radler::math::rms_image {
 
 void Make(gpu::Session& s, float* d_rms_output, const float* d_input, size_t width,
@@ -14,28 +16,18 @@ void Make(gpu::Session& s, float* d_rms_output, const float* d_input, size_t wid
   gpu::Check(rdl_square(s.Handle(), d_input, d_rms_output, n), "rdl_square");
   const long double bmaj = beam_major * window_size, bmin = beam_minor * window_size;
   if (bmaj != 0.0L || bmin != 0.0L) {
-    const long double fwhm_to_sigma = 1.0L / (2.0L * sqrtl(2.0L * logl(2.0L)));
-    const long double sigma_major = bmaj * fwhm_to_sigma;
-    const long double sigma_minor = bmin * fwhm_to_sigma;
-    const long double angle = beam_pa + 0.5L * M_PI;  // from North
-    const double sigma_max = double(std::max(fabsl(sigma_major * cosl(angle)),
-                                             fabsl(sigma_major * sinl(angle))));
-    const size_t min_dim = std::min(width, height);
-    size_t box = std::min<size_t>(
-        size_t(std::ceil(sigma_max * 40.0 /
-                         double(std::min(pixel_scale_l, pixel_scale_m)))),
-        min_dim);
-    if (box % 2 != 0) ++box;
-    if (box > min_dim) box = min_dim;
+    // RestoreImage's kernel geometry (restore.h)
+    const RestoreKernel k =
+        MakeRestoreKernel(width, height, bmaj, bmin, beam_pa, pixel_scale_l, pixel_scale_m);
     // float64 FFT convolution of the float squares and the float kernel,
     // rounded to float once: a float32 transform's rounding (relative to the
     // brightest squares) swamps the faint regions whose RMS sets the factor
     gpu::Fft& fft = s.GetFft(width, height, true);
     gpu::Buffer placed(s, n * sizeof(float));
     gpu::Check(rdl_place_gaussian(s.Handle(), placed.F(), uint32_t(width),
-                                  uint32_t(height), uint32_t(box), double(pixel_scale_l),
-                                  double(pixel_scale_m), double(sigma_major),
-                                  double(sigma_minor), double(angle)),
+                                  uint32_t(height), uint32_t(k.box), double(pixel_scale_l),
+                                  double(pixel_scale_m), k.sigma_major, k.sigma_minor,
+                                  k.angle),
                "rdl_place_gaussian");
     gpu::Buffer spectrum(s, fft.SpectrumBytes());
     if (fft.UsesLds()) {  // float in/out, float64 transforms

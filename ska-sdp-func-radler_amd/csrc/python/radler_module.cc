@@ -19,6 +19,7 @@
 #include "logger.h"
 #include "multiscale_algorithm.h"
 #include "radler.h"
+#include "restore.h"
 #include "rms_image.h"
 #include "component_optimization.h"
 #include "fft_sizes.h"
@@ -462,6 +463,15 @@ void InitRadler(py::module& m) {  // python/pyradler.cc
       });
 }
 
+// planes of one size as a (n_planes, height, width) array
+py::array_t<float> StackImages(const std::vector<aocommon::Image>& planes, size_t width,
+                               size_t height) {
+  py::array_t<float> out({planes.size(), height, width});
+  for (size_t g = 0; g != planes.size(); ++g)
+    std::copy_n(planes[g].Data(), width * height, out.mutable_data() + g * width * height);
+  return out;
+}
+
 void InitComponentList(py::module& m) {  // python/pycomponent_list.cc
   py::class_<radler::ComponentList>(m, "ComponentList")
       .def(py::init<>())
@@ -550,7 +560,85 @@ void InitComponentList(py::module& m) {  // python/pycomponent_list.cc
              std::copy(terms.begin(), terms.end(), out.mutable_data());
              return out;
            },
-           py::arg("scale_index"), py::arg("fitter"), py::arg("device") = false);
+           py::arg("scale_index"), py::arg("fitter"), py::arg("device") = false)
+      .def("render",
+           [](const radler::ComponentList& self,
+              const schaapcommon::fitters::SpectralFitter& fitter,
+              const std::vector<double>& scale_sizes, const std::vector<double>& frequencies,
+              radler::MultiscaleShape shape) {
+             // ComponentList::Render on the default device's session:
+             // (n_planes, height, width). The argument checks come first, so
+             // they are reported where there is no device.
+             self.CheckRender(fitter, scale_sizes, frequencies);
+             std::shared_ptr<radler::gpu::Session> session =
+                 radler::gpu::Session::ForDevice(radler::gpu::Session::DefaultDevice());
+             std::vector<aocommon::Image> planes;
+             {
+               py::gil_scoped_release release;
+               planes = self.Render(fitter, scale_sizes, shape, frequencies, *session);
+             }
+             return StackImages(planes, self.Width(), self.Height());
+           },
+           py::arg("fitter"), py::arg("scale_sizes"),
+           py::arg("frequencies") = std::vector<double>(),
+           py::arg("shape") = radler::MultiscaleShape::kTaperedQuadraticShape)
+      .def("render_model",
+           [](const radler::ComponentList& self, const radler::Radler& radler,
+              const std::vector<double>& frequencies) {
+             // ComponentList::Render with the Radler's fitter, scale sizes,
+             // shape, forced-term planes and session
+             std::vector<aocommon::Image> planes;
+             {
+               py::gil_scoped_release release;
+               planes = self.Render(radler, frequencies);
+             }
+             return StackImages(planes, self.Width(), self.Height());
+           },
+           py::arg("radler"), py::arg("frequencies") = std::vector<double>());
+}
+
+void InitRestore(py::module& m) {
+  m.def(
+      "restore",
+      [](FloatArray image, FloatArray model, long double beam_major, long double beam_minor,
+         long double beam_pa, long double pixel_scale_x, long double pixel_scale_y) {
+        // radler::math::RestoreImage (restore.h) plane by plane on the default
+        // device's session: image + model convolved with the beam, as a new
+        // array. 2-D images, or 3-D stacks restored with the one beam.
+        if (image.ndim() != 2 && image.ndim() != 3)
+          throw std::runtime_error("restore: expected 2-D images or 3-D stacks");
+        if (model.ndim() != image.ndim())
+          throw std::runtime_error("restore: image and model differ in shape");
+        for (py::ssize_t d = 0; d != image.ndim(); ++d)
+          if (image.shape(d) != model.shape(d))
+            throw std::runtime_error("restore: image and model differ in shape");
+        const size_t planes = image.ndim() == 3 ? size_t(image.shape(0)) : 1;
+        const size_t h = image.shape(image.ndim() - 2), w = image.shape(image.ndim() - 1);
+        const size_t n = w * h;
+        py::array_t<float> out(std::vector<py::ssize_t>(image.shape(), image.shape() + image.ndim()));
+        if (planes * n == 0) return out;
+        std::shared_ptr<radler::gpu::Session> session =
+            radler::gpu::Session::ForDevice(radler::gpu::Session::DefaultDevice());
+        radler::gpu::Session& s = *session;
+        const float* h_image = image.data();
+        const float* h_model = model.data();
+        float* h_out = out.mutable_data();
+        {
+          py::gil_scoped_release release;
+          s.Bind();
+          radler::gpu::Buffer d_image(s, n * sizeof(float)), d_model(s, n * sizeof(float));
+          for (size_t p = 0; p != planes; ++p) {
+            s.H2D(d_image.Ptr(), h_image + p * n, n * sizeof(float));
+            s.H2D(d_model.Ptr(), h_model + p * n, n * sizeof(float));
+            radler::math::RestoreImage(s, d_image.F(), d_model.F(), w, h, beam_major,
+                                       beam_minor, beam_pa, pixel_scale_x, pixel_scale_y);
+            s.D2H(h_out + p * n, d_image.Ptr(), n * sizeof(float));
+          }
+        }
+        return out;
+      },
+      py::arg("image"), py::arg("model"), py::arg("beam_major"), py::arg("beam_minor"),
+      py::arg("beam_pa"), py::arg("pixel_scale_x"), py::arg("pixel_scale_y"));
 }
 
 py::dict ResultDict(const radler::algorithms::ParallelDeconvolutionResult& r,
@@ -1178,6 +1266,7 @@ PYBIND11_MODULE(radler, m) {  // python/pywrappers.cc
   InitIo(m);
   InitRadler(m);
   InitComponentList(m);
+  InitRestore(m);
   InitGpu(m);
   InitTiling(m);
   InitDistributed(m);
