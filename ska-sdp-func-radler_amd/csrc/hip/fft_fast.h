@@ -1,5 +1,5 @@
 // Compile-time-planned FFT kernels (fft_fast*.hip): plan lookup and launches
-// used by the LDS engine's host code (lds_fft.hip) for the sizes they cover.
+// used by the convolution object (conv.hip) for the sizes they cover.
 #pragma once
 
 #include <cstddef>

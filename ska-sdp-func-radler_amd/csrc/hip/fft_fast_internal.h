@@ -4,7 +4,7 @@
 // launch function, lives in one unit: fft_fast_cols.hip (Columns),
 // fft_fast_convd.hip (ColumnsConvD), fft_fast_rows.hip (the row kernels),
 // fft_fast_steps.hip (the four-step passes); fft_fast.hip holds the tables
-// made on the host. lds_fft.hip sees fft_fast.h only.
+// made on the host. conv.hip sees fft_fast.h only.
 #pragma once
 
 #include <cstddef>

@@ -1,6 +1,6 @@
 // Device pieces of IuwtDeconvolutionAlgorithm
 // (cpp/algorithms/iuwt_deconvolution_algorithm.cc) that are not the IUWT
-// transform itself (iuwt.hip) or a convolution (lds_fft.hip / fftconv.hip):
+// transform itself (iuwt.hip) or a convolution (conv.hip / fftconv.hip):
 // the structure selection and masking, GetMaxAbs, the conjugate-gradient dot
 // products and SNR sums, the bounding-box scan and precision conversions.
 // All are single streaming passes (HBM-bound, 4-8 B/px); reductions

@@ -445,7 +445,7 @@ void AspAlgorithm::CorrectResidual(float* d_residual, const float* d_component,
     gpu::Buffer& work =
         session.Scratch(gpu::Session::kCorrectionSpectrum, fft.ConvolveSubtractBytes());
     fft.ConvolveSubtract(d_component, width_, height_, (pw - width_) / 2, (ph - height_) / 2,
-                         d_spectrum, work.Ptr(), d_residual, nullptr, !fft.SplitColumns(),
+                         d_spectrum, work.Ptr(), d_residual, nullptr,
                          SubMinorLoop::CorrectionKernelF32() && fft.ConvColumnsD());
     return;
   }

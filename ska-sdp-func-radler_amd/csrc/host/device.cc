@@ -63,19 +63,13 @@ Fft::Fft(Session& s, size_t width, size_t height, bool f64)
   // Perform) and plans in microseconds where rocFFT compiles kernels for
   // 0.2-0.3 s per size. RADLER_FFT=rocfft restores rocFFT.
   const bool want_lds = mode != "rocfft";
-  // RADLER_FFT_COLUMNS=single / split overrides the column-pass choice
-  const char* cols_env = std::getenv("RADLER_FFT_COLUMNS");
-  const std::string cols = cols_env ? cols_env : "";
-  const int strategy = cols == "single"  ? RDL_CONV_COLUMNS_SINGLE
-                       : cols == "split" ? RDL_CONV_COLUMNS_SPLIT
-                                         : RDL_CONV_COLUMNS_AUTO;
-  if (!want_lds || rdl_conv_create_ex(s.Handle(), uint32_t(width), uint32_t(height),
-                                      f64 ? 1 : 0, strategy, &conv_) != RDL_OK)
+  if (!want_lds || rdl_conv_create(s.Handle(), uint32_t(width), uint32_t(height), f64 ? 1 : 0,
+                                   &conv_) != RDL_OK)
     conv_ = nullptr;
   if (conv_) {
     // the compile-time-planned column kernels read and write any layout:
     // spectra are then stored column by column (contiguous column reads)
-    cm_ = (rdl_conv_fast(conv_) & RDL_CONV_FAST_COLUMNS) != 0 && !SplitColumns();
+    cm_ = (rdl_conv_fast(conv_) & RDL_CONV_FAST_COLUMNS) != 0;
     spectrum_bytes_ = rdl_conv_spectrum_bytes(conv_);
   } else {
     conv_ = nullptr;
@@ -264,14 +258,14 @@ void Fft::ForwardColumnMajor(const float* d_in, void* d_spectrum) {
 bool Fft::ConvolveSubtract(const float* d_image, size_t img_w, size_t img_h,
                            size_t ox, size_t oy, const void* d_kernel_spectrum,
                            void* d_work, float* d_residual,
-                           const uint8_t* d_row_mask, bool kernel_col_major,
-                           bool kernel_f32, const PeakRequest* peak) {
+                           const uint8_t* d_row_mask, bool kernel_f32,
+                           const PeakRequest* peak) {
   if (!conv_) throw std::logic_error("Fft::ConvolveSubtract needs the LDS engine");
   const double norm = 1.0 / (double(width_) * double(height_));
   if (peak) {
     const int rc = rdl_conv_convolve_subtract_peak(
         conv_, d_image, uint32_t(img_w), uint32_t(img_h), uint32_t(ox), uint32_t(oy),
-        d_kernel_spectrum, kernel_col_major ? RDL_CONV_COL_MAJOR : RDL_CONV_ROW_MAJOR,
+        d_kernel_spectrum, RDL_CONV_COL_MAJOR,
         kernel_f32 ? 1 : 0, f64_ ? norm : double(float(norm)), d_row_mask, d_work, d_residual,
         peak->h_border, peak->v_border, peak->allow_negative ? 1 : 0, peak->d_mask, 1,
         peak->slot);
@@ -281,7 +275,7 @@ bool Fft::ConvolveSubtract(const float* d_image, size_t img_w, size_t img_h,
   }
   Check(rdl_conv_convolve_subtract(
             conv_, d_image, uint32_t(img_w), uint32_t(img_h), uint32_t(ox), uint32_t(oy),
-            d_kernel_spectrum, kernel_col_major ? RDL_CONV_COL_MAJOR : RDL_CONV_ROW_MAJOR,
+            d_kernel_spectrum, RDL_CONV_COL_MAJOR,
             kernel_f32 ? 1 : 0, f64_ ? norm : double(float(norm)), d_row_mask, d_work,
             d_residual),
         "rdl_conv_convolve_subtract");

@@ -98,7 +98,7 @@ class Fft {
   /// LDS engine only: residual(window) -= Trim(conv(Untrim(image), kernel)),
   /// the image (img_w x img_h) placed at (ox, oy) in the plane.
   /// d_row_mask (plane rows, 0 = the image row is all zero) skips the empty
-  /// rows; kernel_col_major reads a spectrum made by ForwardColumnMajor.
+  /// rows; the kernel spectrum is one made by ForwardColumnMajor.
   /// d_work holds ConvolveSubtractBytes() (the float64 convolution-column
   /// plans keep its spectrum in the tiled layout: rdl_conv_convolve_subtract).
   /// With `peak`: the search of the corrected residual fused into the last
@@ -108,7 +108,7 @@ class Fft {
                         size_t ox, size_t oy, const void* d_kernel_spectrum,
                         void* d_work, float* d_residual,
                         const uint8_t* d_row_mask = nullptr,
-                        bool kernel_col_major = false, bool kernel_f32 = false,
+                        bool kernel_f32 = false,
                         const PeakRequest* peak = nullptr);
   size_t ConvolveSubtractBytes() const;
   /// LDS engine only: forward spectrum stored column by column (column k at
@@ -135,9 +135,6 @@ class Fft {
   /// column by column, which Convolve / ConvolveSpectrum then expect.
   bool ColumnMajorSpectra() const { return cm_; }
   int Layout() const { return cm_ ? RDL_CONV_COL_MAJOR : RDL_CONV_ROW_MAJOR; }
-  /// LDS engine with the split (four-step) column passes: spectra are read
-  /// row-major, so ForwardColumnMajor is not used.
-  bool SplitColumns() const { return conv_ && rdl_conv_columns_split(conv_); }
   /// float64 convolution columns by ff::ColumnsConvD (float kernels allowed)
   bool ConvColumnsD() const { return conv_ && (rdl_conv_fast(conv_) & RDL_CONV_FAST_CONVD); }
   /// Double-precision rocFFT plan only.

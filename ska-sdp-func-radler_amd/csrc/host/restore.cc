@@ -58,10 +58,7 @@ void RestoreImage(gpu::Session& s, float* d_image, const float* d_model, size_t 
   gpu::Check(rdl_scale(s.Handle(), placed.F(), pn, -1.0f), "rdl_scale");
   gpu::Buffer spectrum(s, fft.SpectrumBytes());
   if (fft.UsesLds()) {  // float in, float64 transforms
-    if (fft.SplitColumns())
-      fft.Forward(placed.F(), spectrum.Ptr());
-    else
-      fft.ForwardColumnMajor(placed.F(), spectrum.Ptr());
+    fft.ForwardColumnMajor(placed.F(), spectrum.Ptr());
   } else {  // rocFFT double
     gpu::Buffer placed64(s, pn * sizeof(double));
     gpu::Check(rdl_convert(s.Handle(), placed.F(), placed64.D(), pn, 1), "rdl_convert");

@@ -133,10 +133,7 @@ std::shared_ptr<gpu::Buffer> SubMinorLoop::MakePaddedPsfSpectrum(
                                       uint32_t(ph), d_psf, uint32_t(width),
                                       uint32_t(height)),
                "rdl_prepare_psf_kernel");
-    if (fft.SplitColumns())
-      fft.Forward(kernel.F(), spectrum->Ptr());
-    else
-      fft.ForwardColumnMajor(kernel.F(), spectrum->Ptr());
+    fft.ForwardColumnMajor(kernel.F(), spectrum->Ptr());
   } else {
     gpu::Buffer kernel(s, pw * ph * sizeof(double));
     gpu::Check(rdl_prepare_psf_kernel_f64(s.Handle(), kernel.D(), uint32_t(pw),
@@ -225,7 +222,6 @@ bool SubMinorLoop::CorrectResidualDirtyWithSpectrum(size_t image_index,
                "rdl_subminor_model_masked");
     return fft.ConvolveSubtract(model.F(), width_, height_, ox, oy, d_spectrum, work.Ptr(),
                                 d_residual, static_cast<const uint8_t*>(rows.Ptr()),
-                                !fft.SplitColumns(),
                                 CorrectionKernelF32() && fft.ConvColumnsD(), peak);
   }
   if (!fft.IsF64()) {  // rocFFT float (RDL_CORR_F32=1 at a size the LDS engine lacks)
