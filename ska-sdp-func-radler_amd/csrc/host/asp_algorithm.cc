@@ -10,11 +10,11 @@
 #include "fft_sizes.h"
 #include "host_profile.h"
 #include "logger.h"
+#include "scale_search.h"
 #include "subminor.h"
 
 namespace radler::algorithms {
 
-using multiscale::MultiScaleTransforms;
 using schaapcommon::math::Ellipse;
 
 namespace {
@@ -53,85 +53,37 @@ void AspAlgorithm::FindScaleConvolvedMaxima(const ImageSet& image_set, float* d_
   image_set.GetLinearIntegrated(d_integrated);
   if (scale_infos_.size() > RDL_PEAK_SLOTS)
     throw std::runtime_error("AspAlgorithm: too many scales");
-  const uint32_t hb = uint32_t(std::round(w * CleanBorderRatio()));
-  const uint32_t vb = uint32_t(std::round(h * CleanBorderRatio()));
-  auto borders = [&](float scale, uint32_t& xb, uint32_t& yb) {
-    // ThreadedDeconvolutionTools::FindMultiScalePeak's box: the clean border
-    // or half the scale, whichever is larger
-    const size_t border_scale = size_t(std::ceil(scale * 0.5));
-    xb = uint32_t(std::max<size_t>(hb, border_scale));
-    yb = uint32_t(std::max<size_t>(vb, border_scale));
-  };
+  auto search_input = [&](const float* d_image) { return PeakSearchInput(d_image); };
   std::vector<size_t> pending;  // the scale of each queued search (slot = index)
-  std::vector<size_t> convolved;
-  std::vector<float> scales;
+  std::vector<ConvolvedScale> convolved;
   for (size_t si = 0; si != scale_infos_.size(); ++si) {
-    if (scale_infos_[si].scale == 0.0f) {
+    const float scale = scale_infos_[si].scale;
+    if (scale == 0.0f) {
       // FindPeakDirect (:412-458): the delta scale is not convolved
-      gpu::Check(rdl_find_peak_enqueue(s, PeakSearchInput(d_integrated), uint32_t(w),
-                                       uint32_t(h), 0, uint32_t(h), hb, vb,
+      const Borders border = PeakBorders(w, h);
+      gpu::Check(rdl_find_peak_enqueue(s, search_input(d_integrated), uint32_t(w), uint32_t(h),
+                                       0, uint32_t(h), border.horizontal, border.vertical,
                                        AllowNegativeComponents(), d_mask_, 1,
                                        uint32_t(pending.size())),
                  "rdl_find_peak_enqueue");
       pending.push_back(si);
     } else {
-      convolved.push_back(si);
-      scales.push_back(scale_infos_[si].scale);
+      // every scale is searched, into the one scratch image, inside the one mask
+      convolved.push_back({si, scale, scratch_->F(), d_mask_, PeakBorders(w, h, scale)});
     }
   }
   if (!convolved.empty()) {
-    const bool fused = !RmsFactorImage() && transforms_->Fused();
-    if (fused) {
-      // every scale's convolution from one forward half (rdl_conv_scales),
-      // then per scale the outer inverse and the rows with the fused search
-      const size_t sb = transforms_->SpectrumBytes();
-      while (scale_u_.size() < convolved.size())
-        scale_u_.push_back(std::make_shared<gpu::Buffer>(*session_, sb));
-      std::vector<void*> outs;
-      for (size_t k = 0; k != convolved.size(); ++k) outs.push_back(scale_u_[k]->Ptr());
-      for (float sc : scales) transforms_->RealKernelSpectrum(sc);
-      transforms_->ForwardHalf(d_integrated, spectrum_->Ptr());
-      transforms_->Scales(spectrum_->Ptr(), scales, outs);
-      for (size_t k = 0; k != convolved.size(); ++k) {
-        uint32_t xb, yb;
-        borders(scales[k], xb, yb);
-        transforms_->FinishPeak(outs[k], scales[k], spectrum_work_->Ptr(), scratch_->F(), xb,
-                                yb, AllowNegativeComponents(), d_mask_,
-                                uint32_t(pending.size()));
-        pending.push_back(convolved[k]);
-      }
-    } else {
-      transforms_->Forward(d_integrated, spectrum_->Ptr());
-      for (size_t k = 0; k != convolved.size(); ++k) {
-        uint32_t xb, yb;
-        borders(scales[k], xb, yb);
-        const uint32_t slot = uint32_t(pending.size());
-        if (RmsFactorImage() ||
-            !transforms_->ConvolveSpectrumPeak(spectrum_->Ptr(), scales[k],
-                                               spectrum_work_->Ptr(), scratch_->F(), xb, yb,
-                                               AllowNegativeComponents(), d_mask_, slot)) {
-          transforms_->ConvolveSpectrum(spectrum_->Ptr(), scales[k], spectrum_work_->Ptr(),
-                                        scratch_->F());
-          gpu::Check(rdl_find_peak_enqueue(s, PeakSearchInput(scratch_->F()), uint32_t(w),
-                                           uint32_t(h), 0, uint32_t(h), xb, yb,
-                                           AllowNegativeComponents(), d_mask_, 1, slot),
-                     "rdl_find_peak_enqueue");
-        }
-        pending.push_back(convolved[k]);
-      }
-    }
+    ScaleSearch search{*session_, *transforms_, spectrum_->Ptr(),
+                       {spectrum_work_->Ptr(), nullptr},  // no lanes
+                       scale_u_, AllowNegativeComponents()};
+    if (!RmsFactorImage() && transforms_->Fused())
+      search.Fused(d_integrated, convolved, false, pending);
+    else
+      search.ThroughSpectrum(d_integrated, convolved, !RmsFactorImage(), false, pending,
+                             search_input);
   }
-  std::vector<rdl_peak> peaks(pending.size());
-  gpu::Check(rdl_find_peak_collect(s, uint32_t(pending.size()), peaks.data()),
-             "rdl_find_peak_collect");
-  for (size_t k = 0; k != pending.size(); ++k) {
-    ScaleInfo& e = scale_infos_[pending[k]];
-    const rdl_peak& p = peaks[k];
-    e.max_unnormalized_image_value = p.found ? p.value : 0.0f;
-    e.max_normalized_image_value = p.found ? Normalized(p.value, p.x, p.y) : 0.0f;
-    e.max_image_value_x = p.x;
-    e.max_image_value_y = p.y;
-  }
+  CollectPeaks(s, pending, scale_infos_,
+               [&](float v, size_t x, size_t y) { return Normalized(v, x, y); });
 }
 
 DeconvolutionResult AspAlgorithm::ExecuteMajorIteration(ImageSet& data_image,
@@ -159,17 +111,8 @@ DeconvolutionResult AspAlgorithm::ExecuteMajorIteration(ImageSet& data_image,
                                             settings_.convolution_padding);
   padded_height_ = utils::GetConvolutionSize(scale_infos_.back().scale, height,
                                              settings_.convolution_padding);
-  if (!transforms_ || !transforms_->BoundTo(session) || transforms_->Width() != width ||
-      transforms_->Height() != height) {
-    transforms_ =
-        std::make_unique<MultiScaleTransforms>(session, width, height, settings_.shape);
+  if (EnsureTransforms(transforms_, session, width, height, settings_.shape, &scale_infos_))
     scale_u_.clear();
-  }
-  {
-    float max_scale = 0.0f;
-    for (const ScaleInfo& e : scale_infos_) max_scale = std::max(max_scale, e.scale);
-    transforms_->SetMaxScale(max_scale);
-  }
   d_mask_ = DeviceCleanMask(session, width, height);
   scratch_ = std::make_shared<gpu::Buffer>(session, npx * sizeof(float));
   rms_scratch_.reset();

@@ -9,6 +9,7 @@
 #include <optional>
 #include <vector>
 
+#include "clean_border.h"
 #include "device.h"
 #include "image_set.h"
 #include "settings.h"
@@ -69,6 +70,11 @@ class DeconvolutionAlgorithm {
   float MinorLoopGain() const { return settings_.minor_loop_gain; }
   float MajorLoopGain() const { return settings_.major_loop_gain; }
   float CleanBorderRatio() const { return settings_.clean_border_ratio; }
+  /// The clean border of a width x height image (clean_border.h), for the
+  /// search of an image convolved with `scale` at least half that scale.
+  Borders PeakBorders(size_t width, size_t height, float scale = 0.0f) const {
+    return CleanBorders(width, height, CleanBorderRatio(), scale);
+  }
   bool AllowNegativeComponents() const {
     return settings_.allow_negative_components;
   }

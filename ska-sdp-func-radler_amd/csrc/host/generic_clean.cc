@@ -26,11 +26,10 @@ rdl_peak GenericClean::FindPeak(gpu::Session& s, const float* d_image,
       rms_scratch_ = std::make_shared<gpu::Buffer>(s, width * height * sizeof(float));
     d_image = RmsWeighted(s, d_image, rms_scratch_->F(), width, height);
   }
-  const uint32_t hb = uint32_t(std::round(width * CleanBorderRatio()));
-  const uint32_t vb = uint32_t(std::round(height * CleanBorderRatio()));
+  const Borders border = PeakBorders(width, height);
   rdl_peak p;
-  gpu::Check(rdl_find_peak(s.Handle(), d_image, uint32_t(width),
-                           uint32_t(height), 0, uint32_t(height), hb, vb,
+  gpu::Check(rdl_find_peak(s.Handle(), d_image, uint32_t(width), uint32_t(height), 0,
+                           uint32_t(height), border.horizontal, border.vertical,
                            AllowNegativeComponents(), d_mask, 1, &p),
              "rdl_find_peak");
   return p;
@@ -155,8 +154,8 @@ DeconvolutionResult GenericClean::ExecuteMajorIteration(
     sub.SetSpectralMap(DeviceSpectralMap(s, dirty_set.Size()));
     sub.SetLogPolyFit(DeviceFit(s, width, height));
     sub.SetRmsFactor(DeviceRmsFactor(s, width, height));  // :126-128
-    sub.SetCleanBorders(size_t(std::round(width * CleanBorderRatio())),
-                        size_t(std::round(height * CleanBorderRatio())));
+    const Borders border = PeakBorders(width, height);
+    sub.SetCleanBorders(border.horizontal, border.vertical);
     sub.SetTrace(&trace_);  // (kept for GenericClean: not on the headline path)
     const SubMinorLoop::RunResult r = sub.Run(dirty_set, psfs);
     diverging = r.diverging;
@@ -192,8 +191,8 @@ DeconvolutionResult GenericClean::ExecuteMajorIteration(
     p.max_iterations = MaxIterations();
     p.allow_negative = AllowNegativeComponents();
     p.stop_on_negative = StopOnNegativeComponents();
-    p.h_border = uint32_t(std::round(width * CleanBorderRatio()));
-    p.v_border = uint32_t(std::round(height * CleanBorderRatio()));
+    p.h_border = PeakBorders(width, height).horizontal;
+    p.v_border = PeakBorders(width, height).vertical;
     p.d_mask = d_mask;
     p.d_spectral = DeviceSpectralMap(s, dirty_set.Size());
     p.logpoly = DeviceFit(s, width, height);

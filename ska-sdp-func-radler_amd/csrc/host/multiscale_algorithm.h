@@ -6,7 +6,9 @@
 // convolutions): the forward FFT of the integrated image is shared by all
 // active scales, twice-convolved PSFs and padded PSF spectra are computed once
 // per scale, and kept over the major iterations whose PSFs are the same
-// (PsfCache).
+// (MultiScalePsfProducts, multiscale_psf_products.h). ExecuteMajorIteration
+// is a sequence of named steps (the private section below); what its peak
+// searches share with AspAlgorithm's is in scale_search.h.
 #pragma once
 
 #include <map>
@@ -16,7 +18,9 @@
 
 #include "component_list.h"
 #include "deconvolution_algorithm.h"
+#include "multiscale_psf_products.h"
 #include "multiscale_transforms.h"
+#include "subminor.h"
 
 namespace radler::algorithms {
 
@@ -92,9 +96,88 @@ class MultiScaleAlgorithm final : public DeconvolutionAlgorithm {
   }
 
  private:
+  // The environment's switches (multiscale_algorithm.cc, top), read once per
+  // major iteration, so a test can compare both sides in one process.
+  struct Switches {
+    int scale_lanes;
+    bool fused_scales, corr_peak, psf_cache, model_gate;
+    size_t psf_cache_budget;
+  };
+  // What the steps of one major iteration share.
+  struct Iteration {
+    ImageSet& data;
+    ImageSet& model;
+    float* d_integrated;  // W x H
+    // joined channels over the ranks of shard_ (SetChannelShard): image i's
+    // residual correction and model update run on rank i % size only
+    int n_ranks, my_rank;
+    bool sharded;
+    int Owner(size_t i) const { return sharded ? int(i % size_t(n_ranks)) : my_rank; }
+    float initial_peak_value = 0.0f;
+    float first_threshold = 0.0f;
+    bool diverging = false;
+    bool has_hit_threshold_in_sub_loop = false;
+    size_t threshold_countdown = 0;
+  };
+  // the tracked masks go back to the host copies on every return
+  struct MaskSync {
+    MultiScaleAlgorithm* a;
+    ~MaskSync() {
+      if (a->track_masks_) a->DownloadScaleMasks();
+    }
+  };
+
+  // ExecuteMajorIteration's steps, in its order
+  void SetUpScalesAndMasks(ImageSet& data_image);
+  /// The transforms, the clean mask, the scratch image, the spectra, the
+  /// lanes. Returns the W x H buffer of the integrated image, which goes when
+  /// the major iteration returns.
+  gpu::Buffer SetUpBuffers(ImageSet& data_image);
+  /// every scale's PSF peak, bias factor and gain (:29-88, the scalars)
+  void SetUpScalePsfs();
+  /// the major iteration's threshold from its first peak; whether it is final
+  bool StartThresholds(Iteration& it, const ScaleInfo& first);
+  /// the sub-minor loop's threshold for `info`; counts down the loops that
+  /// ran into the major iteration's threshold
+  float SubIterationThreshold(Iteration& it, const ScaleInfo& info);
+  /// `individual` = the images convolved with the scale (:336-354)
+  void IndividualImages(ImageSet& individual, const ImageSet& data_image, size_t scale_index);
+  /// :377-462. False: the loop found no component. `searched`: the next peak
+  /// searches already ran (deferred result).
+  bool FastSubMinorStep(Iteration& it, size_t scale_index, float threshold,
+                        ImageSet& individual, const gpu::Planes& twice, bool& searched);
+  void ConfigureSubMinorLoop(SubMinorLoop& sub, Iteration& it, size_t scale_index,
+                             float threshold);
+  /// a finished loop's result into the iteration count, the scale's totals
+  /// and `it.diverging`
+  void Account(Iteration& it, SubMinorLoop& sub, ScaleInfo& info, size_t sub_start,
+               const SubMinorLoop::RunResult& result);
+  /// the next scale-0 search as a request to the residual correction, where
+  /// the correction can make it (one image that is its own integrated image)
+  std::optional<gpu::PeakRequest> Scale0PeakRequest(const ImageSet& data_image) const;
+  /// the residual correction and the model update of this rank's images
+  void CorrectAndModel(Iteration& it, SubMinorLoop& sub, size_t scale_index, size_t sub_start,
+                       size_t conv_w, size_t conv_h, bool model_after_result);
+  void AddScaleModel(Iteration& it, SubMinorLoop& sub, float scale, size_t sub_start,
+                     size_t image);
+  /// :463-519, a component per pass
+  void SlowSubMinorStep(Iteration& it, size_t scale_index, float threshold,
+                        ImageSet& individual, const gpu::Planes& twice);
+  void LogScalePeaks() const;
+  /// the owners' planes to every rank (stream-ordered on the session; the
+  /// ranks issue the same broadcasts in the same order)
+  void SharePlanes(const Iteration& it, ImageSet& set);
+
   void FindActiveScaleConvolvedMaxima(const ImageSet& image_set,
                                       float* d_integrated, bool report_rms);
   void FindPeakDirect(const float* d_image, size_t scale_index);
+  /// d_image, or d_image x the RMS factor (multiscale_algorithm.cc:707-713)
+  const float* PeakSearchInput(const float* d_image, size_t w, size_t h);
+  /// unnormalized / factor at the peak (:736-743), the value itself without
+  float Normalized(float value, size_t x, size_t y, size_t w) const;
+  /// the image FindActiveScaleConvolvedMaxima keeps of the residual
+  /// convolved with scale `scale_index`, made if missing or of another size
+  float* KeptScaleImage(size_t scale_index, size_t w, size_t h);
   void RunFullComponentFitter(ImageSet& residual_set, ImageSet& model_set,
                               const gpu::Planes& psfs);
   void ActivateScales(size_t scale_with_last_peak);
@@ -116,17 +199,12 @@ class MultiScaleAlgorithm final : public DeconvolutionAlgorithm {
 
   // per-major-iteration device state
   gpu::Session* session_ = nullptr;
+  Switches switches_{};
   Communicator* shard_ = nullptr;  // SetChannelShard (not copied by Clone)
   std::unique_ptr<multiscale::MultiScaleTransforms> transforms_;
   const uint8_t* d_mask_ = nullptr;
   std::shared_ptr<gpu::Buffer> scratch_;  // W x H
   std::shared_ptr<gpu::Buffer> rms_scratch_;  // W x H: image x RMS factor
-  /// d_image, or d_image x the RMS factor (multiscale_algorithm.cc:707-713)
-  /// FindActiveScaleConvolvedMaxima through the fused multi-scale launch
-  void FindMaximaFused(const float* d_source, bool identity, std::vector<size_t> pending);
-  const float* PeakSearchInput(const float* d_image, size_t w, size_t h);
-  /// unnormalized / factor at the peak (:736-743), the value itself without
-  float Normalized(float value, size_t x, size_t y, size_t w) const;
   std::shared_ptr<gpu::Buffer> spectrum_, spectrum_work_;
   // the second session lane's work spectrum (FindActiveScaleConvolvedMaxima
   // alternates the scales' fused inverse transforms over two lanes)
@@ -148,33 +226,9 @@ class MultiScaleAlgorithm final : public DeconvolutionAlgorithm {
   // with a PeakRequest), so the residual is not read again for it.
   bool scale0_search_queued_ = false;
 
-  // The PSF-derived products of a major iteration, kept for the next one on a
-  // main session while the PSFs, the scales and the sizes stay the same (the
-  // PSF of a deconvolution does not change between its major iterations). A
-  // worker session's clones and RDL_PSF_CACHE=0 drop them on every return.
-  struct PsfCache {
-    // the key: everything the products depend on; the PSFs by content
-    // (`reference`: the integrated PSF, then every PSF plane, compared bit
-    // for bit on the device)
-    gpu::Session* session = nullptr;
-    size_t width = 0, height = 0, n_psf = 0;
-    std::vector<float> scales;
-    MultiscaleShape shape{};
-    double convolution_padding = 0.0;
-    bool correction_f64 = true, correction_kernel_f32 = false;
-    gpu::Planes reference;
-    // the products
-    std::vector<float> psf_peak;         // per scale (ConvolvePsfs, :29-88)
-    std::vector<gpu::Planes> convolved;  // [psf][scale]
-    std::map<size_t, gpu::Planes> twice;  // scale -> [psf], filled when first used
-    std::map<std::pair<size_t, size_t>, std::shared_ptr<gpu::Buffer>> padded;  // (psf, scale)
-    size_t bytes = 0;  // held by the above, against RDL_PSF_CACHE_MB
-  };
-  PsfCache psf_cache_;
-  /// whether psf_cache_ holds the products of these PSFs (queues the content
-  /// comparison and waits for it)
-  bool PsfCacheHit(gpu::Session& session, size_t width, size_t height, size_t n_psf,
-                   const float* d_integrated_psf, const gpu::Planes& psfs);
+  // ConvolvePsfs (:29-88) and what is made from it, kept over the major
+  // iterations on a main session
+  MultiScalePsfProducts psf_products_;
 
   bool track_masks_ = false, use_masks_ = false;
   std::vector<std::vector<uint8_t>> host_masks_;

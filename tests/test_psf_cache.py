@@ -1,7 +1,7 @@
 """The PSF-derived products of a multiscale major iteration (scale-convolved
 PSFs, twice-convolved PSFs, padded PSF spectra, the per-scale PSF peaks) are
 kept for the next major iteration while the PSFs, the scales and the sizes
-stay the same (MultiScaleAlgorithm::PsfCache). A kept product is the product
+stay the same (MultiScalePsfProducts). A kept product is the product
 that would be made again from the same inputs by the same kernels, so runs
 with the cache (default) and without it (RDL_PSF_CACHE=0) are bit-identical;
 the PSFs are compared by content, so a PSF changed by one ulp between two
@@ -191,3 +191,20 @@ def test_a_budget_too_small_for_anything(rd, reference):
     same(small, reference)
     assert made_again(small["profile"]) == 1
     assert "ms.psf_cache_check" not in small["profile"]
+
+
+@pytest.mark.gpu
+def test_a_budget_that_fits_the_convolved_set_only(rd):
+    """512^2 float planes are 1 MiB each. One PSF and three scales: the
+    convolved set with its reference copies is 3 + 1 + 1 = 5 planes, which a
+    5 MiB budget holds to the byte, and no later product (a twice-convolved
+    plane is 1 MiB more). The second major iteration then hits, and makes the
+    products that did not fit again."""
+    kw = dict(w=512, scale_list=[0.0, 6.0, 20.0])
+    off = two_major_iterations(rd, OFF, **kw)
+    part = two_major_iterations(rd, {"RDL_PSF_CACHE": "1", "RDL_PSF_CACHE_MB": "5"}, **kw)
+    same(part, off)
+    prof = part["profile"]
+    assert prof.get("ms.psf_cache_check", (0, 0.0))[0] == 1
+    assert "ms.convolve_psfs" not in prof
+    assert prof.get("ms.twice_convolved", (0, 0.0))[0] >= 1
