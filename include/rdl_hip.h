@@ -511,8 +511,12 @@ typedef struct {
   uint64_t iteration_start, max_iterations;
   const uint8_t* d_mask;   /* may be NULL */
   /* PerformSpectralFit of each component's gain-scaled values
-   * (subminor_loop.cc:64-76) as an n_images x n_images row-major linear map;
-   * NULL = no fitting */
+   * (subminor_loop.cc:64-76) as an n_images x n_images row-major linear map
+   * S; NULL = no fitting. With r[q] the component's residual value in image
+   * q, image k's component value is computed in float as
+   *   acc = 0; for q = 0 .. n_images - 1: acc = fmaf(S[k][q], r[q] * gain, acc)
+   * (q ascending, the product r[q] * gain rounded before the fused
+   * multiply-add), the same in every loop kernel. */
   const float* d_spectral;
   /* SubMinorLoop::SetRmsFactorImage: W x H factors multiplied into the
    * selection and the loop's argmax (subminor_loop.cc:13-36, 143-149);
@@ -568,11 +572,11 @@ int rdl_subminor_collect(rdl_subminor* h, rdl_subminor_result* out);
 /* Kernel choice for rdl_subminor_run (results are identical): mode 0 picks
  * automatically, 1 forces the LDS-resident loop, 2 the register-resident
  * loop, 3 the single-wave loop, 4 one 1024-thread workgroup, 5 a grid of
- * 1024-thread workgroups, 6 the single-workgroup pairwise-table loop (one
- * image, identity integration, no RMS / spectral / log-polynomial fit, at
- * most 8192 pixels); target_per_block (0 = keep) sets the selected pixels
- * per workgroup above which the register loop spreads over more workgroups
- * (mode 6: 512 or 1024 picks the workgroup size). */
+ * 1024-thread workgroups, 6 the pairwise-table loop (one image, identity
+ * integration, no RMS / spectral / log-polynomial fit, at most 16384 pixels:
+ * the largest selection given a pairwise table); target_per_block (0 = keep)
+ * sets the selected pixels per workgroup above which the register loop
+ * spreads over more workgroups (mode 6: the pixels per participant). */
 int rdl_subminor_set_tuning(rdl_subminor* h, int mode, uint32_t target_per_block);
 
 /* SubMinorLoop::GetFullIndividualModel (subminor_loop.cc:186-193), fused

@@ -712,3 +712,102 @@ extern "C" uint64_t orc_parallel_margins(void* h, float* out, float* values,
   if (values) std::copy_n(vals.data(), n, values);
   return all.size();
 }
+
+// SubMinorLoop::Run alone (oracle.h), with every option set by the caller:
+// GenericCleanExecute reaches it only with a derived threshold, from
+// iteration 0 and without flux_cleaned.
+extern "C" {
+
+struct orc_subminor_params {
+  float threshold, gain, divergence_limit;
+  int32_t allow_negative, stop_on_negative, pad0;
+  uint64_t h_border, v_border, iteration_start, max_iterations;
+  const uint8_t* mask;        // width x height bytes, or NULL
+  const float* rms_factor;    // width x height, or NULL
+  const float* spectral_map;  // n_img x n_img row-major (SubMinorLoop::spectral_map), or NULL
+};
+
+struct orc_subminor_result {
+  uint64_t n_selected, iteration, n_trace;
+  int32_t has_peak;
+  float peak;
+  int32_t diverging;
+  float flux_cleaned;
+};
+
+struct OrcSubminor {
+  std::vector<uint32_t> positions;  // packed y << 16 | x
+  std::vector<float> model;         // [n_img][n_selected]
+  std::vector<uint32_t> trace;      // x, y per component
+  std::vector<float> margins, values;  // per component, then the end of the run
+};
+
+// residual: n_channels * n_pol planes (not modified); psfs: n_channels planes.
+// Returns a handle for orc_subminor_fetch (NULL on error).
+void* orc_subminor_run(const orc_set_desc* d, const float* residual, const float* psfs,
+                       const orc_subminor_params* p, orc_subminor_result* out) {
+  try {
+    SetDesc desc = MakeDesc(d);
+    ImageSet res = MakeSet(desc, d, const_cast<float*>(residual));
+    std::vector<const float*> psf_ptrs;
+    for (uint64_t c = 0; c != d->n_channels; ++c)
+      psf_ptrs.push_back(psfs + c * d->width * d->height);
+    SubMinorLoop sub(d->width, d->height, d->width, d->height);
+    sub.threshold = p->threshold;
+    sub.gain = p->gain;
+    sub.divergence_limit = p->divergence_limit;
+    sub.horizontal_border = p->h_border;
+    sub.vertical_border = p->v_border;
+    sub.current_iteration = p->iteration_start;
+    sub.max_iterations = p->max_iterations;
+    sub.allow_negative = p->allow_negative != 0;
+    sub.stop_on_negative = p->stop_on_negative != 0;
+    sub.mask = reinterpret_cast<const bool*>(p->mask);
+    sub.rms_factor = p->rms_factor;
+    sub.spectral_map = p->spectral_map;
+    std::vector<Component> tr;
+    MarginTracker margins;
+    sub.trace = &tr;
+    sub.margins = &margins;
+    const SubMinorLoop::RunResult r = sub.Run(res, psf_ptrs);
+    auto h = std::make_unique<OrcSubminor>();
+    for (const auto& xy : sub.Positions())
+      h->positions.push_back(uint32_t(xy.second) << 16 | uint32_t(xy.first));
+    for (const std::vector<float>& m : sub.Model()) h->model.insert(h->model.end(), m.begin(), m.end());
+    for (const Component& c : tr) {
+      h->trace.push_back(c.x);
+      h->trace.push_back(c.y);
+      h->margins.push_back(c.margin);
+      h->values.push_back(c.value);
+    }
+    h->margins.push_back(margins.Take());  // the decisions that ended the run
+    h->values.push_back(std::fabs(r.peak));
+    out->n_selected = sub.NSelected();
+    out->iteration = sub.current_iteration;
+    out->n_trace = tr.size();
+    out->has_peak = r.has_peak;
+    out->peak = r.peak;
+    out->diverging = r.diverging;
+    out->flux_cleaned = sub.flux_cleaned;
+    return h.release();
+  } catch (std::exception& e) {
+    g_error = e.what();
+    return nullptr;
+  }
+}
+
+// Any pointer may be NULL. positions: n_selected; model: n_img * n_selected;
+// trace: 2 * n_trace; margins, values: n_trace + 1.
+void orc_subminor_fetch(void* handle, uint32_t* positions, float* model, uint32_t* trace,
+                        float* margins, float* values) {
+  const auto* h = static_cast<const OrcSubminor*>(handle);
+  if (positions) std::copy(h->positions.begin(), h->positions.end(), positions);
+  if (model) std::copy(h->model.begin(), h->model.end(), model);
+  if (trace) std::copy(h->trace.begin(), h->trace.end(), trace);
+  if (margins) std::copy(h->margins.begin(), h->margins.end(), margins);
+  if (values) std::copy(h->values.begin(), h->values.end(), values);
+}
+
+void orc_subminor_free(void* handle) { delete static_cast<OrcSubminor*>(handle); }
+
+}  // extern "C"

@@ -575,8 +575,19 @@ SubMinorLoop::RunResult SubMinorLoop::Run(
                         margins ? margins->Take()
                                 : std::numeric_limits<float>::infinity(),
                         std::fabs(max_value)});
-    PerformSpectralFit(convolved_residual.desc->fitter.get(),
-                       convolved_residual.desc->n_pol, component_values.data());
+    if (spectral_map) {
+      std::vector<float> mapped(n_img);
+      for (size_t k = 0; k != n_img; ++k) {
+        float acc = 0.0f;
+        for (size_t q = 0; q != n_img; ++q)
+          acc = std::fmaf(spectral_map[k * n_img + q], component_values[q], acc);
+        mapped[k] = acc;
+      }
+      component_values = mapped;
+    } else {
+      PerformSpectralFit(convolved_residual.desc->fitter.get(),
+                         convolved_residual.desc->n_pol, component_values.data());
+    }
     for (size_t i = 0; i != n_img; ++i)
       model_[i][max_component] += component_values[i];
     for (size_t i = 0; i != n_img; ++i) {

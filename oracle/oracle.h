@@ -186,6 +186,11 @@ class SubMinorLoop {
   bool allow_negative = true, stop_on_negative = false;
   const bool* mask = nullptr;
   const float* rms_factor = nullptr;  // SetRmsFactorImage (full image)
+  // Tests only: an n_img x n_img row-major float map applied to each
+  // component's gain-scaled values in place of PerformSpectralFit:
+  // c[k] = sum over q ascending of fmaf(S[k][q], r[q] * gain, acc), acc from
+  // 0, in float (the C-ABI's definition of d_spectral, include/rdl_hip.h)
+  const float* spectral_map = nullptr;
   float flux_cleaned = 0.0f;
   std::vector<Component>* trace = nullptr;
   uint32_t trace_scale = 0;
@@ -206,6 +211,10 @@ class SubMinorLoop {
   // value in any image joins the mask
   void UpdateAutoMask(bool* mask) const;
   size_t NSelected() const { return positions_.size(); }
+  // the selected pixels (x, y) in selection order, and their model values
+  // per image
+  const std::vector<std::pair<size_t, size_t>>& Positions() const { return positions_; }
+  const std::vector<std::vector<float>>& Model() const { return model_; }
 
  private:
   size_t width_, height_, padded_width_, padded_height_;

@@ -47,6 +47,31 @@ class Result(C.Structure):
                 ("iteration_number", C.c_uint64), ("n_trace", C.c_uint64)]
 
 
+class SubminorRunParams(C.Structure):
+    """orc_subminor_params (oracle/capi.cc)."""
+    _fields_ = [("threshold", C.c_float), ("gain", C.c_float), ("divergence_limit", C.c_float),
+                ("allow_negative", C.c_int32), ("stop_on_negative", C.c_int32),
+                ("pad0", C.c_int32),
+                ("h_border", C.c_uint64), ("v_border", C.c_uint64),
+                ("iteration_start", C.c_uint64), ("max_iterations", C.c_uint64),
+                ("mask", C.c_void_p), ("rms_factor", C.c_void_p),
+                ("spectral_map", C.c_void_p)]
+
+
+class SubminorRunResult(C.Structure):
+    _fields_ = [("n_selected", C.c_uint64), ("iteration", C.c_uint64), ("n_trace", C.c_uint64),
+                ("has_peak", C.c_int32), ("peak", C.c_float), ("diverging", C.c_int32),
+                ("flux_cleaned", C.c_float)]
+
+
+class SubminorRun:
+    """What Oracle.subminor_run returns: n_selected, positions (packed
+    y << 16 | x, selection order), model [n_img, n_selected], trace [n, 2]
+    (x, y), margins and values [n + 1] (oracle.h Component::margin / value per
+    component, then the decisions that ended the run and the final |peak|),
+    has_peak, peak, diverging, iteration, flux_cleaned."""
+
+
 def algo_settings(**kw):
     """Defaults of DeconvolutionAlgorithm (cpp/algorithms/deconvolution_algorithm.h:187-199)
     and Settings::Multiscale (cpp/settings.h:465-524)."""
@@ -327,6 +352,62 @@ class Oracle:
         L.orc_spectral_interpolate(int(mode), int(n_terms), f.ctypes.data, w.ctypes.data,
                                    f.size, p.ctypes.data, int(np.prod(p.shape[1:])),
                                    of.ctypes.data, of.size, out.ctypes.data)
+        return out
+
+    def subminor_run(self, residual, psfs, threshold, gain=0.1, divergence_limit=4.0,
+                     h_border=0, v_border=0, iteration_start=0, max_iterations=500,
+                     allow_negative=True, stop_on_negative=False, mask=None, rms_factor=None,
+                     spectral_map=None, n_pol=1, weights=None, pol_factor=1.0, spectral=None):
+        """SubMinorLoop::Run alone. residual: (n_img, h, w), images ordered
+        channel * n_pol + pol; psfs: (n_img // n_pol, h, w). spectral: the
+        set's fitter as in set_desc; spectral_map: an n_img x n_img float map
+        applied instead of it. Returns a SubminorRun."""
+        residual = np.ascontiguousarray(residual, np.float32)
+        psfs = np.ascontiguousarray(psfs, np.float32)
+        n, h, w = residual.shape
+        assert n % n_pol == 0 and psfs.shape == (n // n_pol, h, w)
+        d = self.set_desc(w, h, n // n_pol, n_pol, weights, pol_factor, spectral=spectral)
+        p = SubminorRunParams()
+        p.threshold, p.gain, p.divergence_limit = threshold, gain, divergence_limit
+        p.allow_negative, p.stop_on_negative = int(allow_negative), int(stop_on_negative)
+        p.h_border, p.v_border = h_border, v_border
+        p.iteration_start, p.max_iterations = iteration_start, max_iterations
+        keep = []
+        for name, arr, dtype, shape in (("mask", mask, np.uint8, (h, w)),
+                                        ("rms_factor", rms_factor, np.float32, (h, w)),
+                                        ("spectral_map", spectral_map, np.float32, (n, n))):
+            if arr is not None:
+                a = np.ascontiguousarray(arr, dtype)
+                assert a.shape == shape, (name, a.shape)
+                keep.append(a)
+                setattr(p, name, a.ctypes.data)
+        L = self.lib
+        L.orc_subminor_run.restype = C.c_void_p
+        L.orc_subminor_run.argtypes = [C.POINTER(SetDesc), f32p, f32p,
+                                       C.POINTER(SubminorRunParams),
+                                       C.POINTER(SubminorRunResult)]
+        L.orc_subminor_fetch.restype = None
+        L.orc_subminor_fetch.argtypes = [C.c_void_p] * 6
+        L.orc_subminor_free.restype = None
+        L.orc_subminor_free.argtypes = [C.c_void_p]
+        r = SubminorRunResult()
+        handle = L.orc_subminor_run(C.byref(d), residual, psfs, C.byref(p), C.byref(r))
+        if not handle:
+            raise RuntimeError(L.orc_last_error().decode())
+        n_sel, n_tr = int(r.n_selected), int(r.n_trace)
+        out = SubminorRun()
+        out.n_selected, out.iteration = n_sel, int(r.iteration)
+        out.has_peak, out.peak = int(r.has_peak), np.float32(r.peak)
+        out.diverging, out.flux_cleaned = int(r.diverging), np.float32(r.flux_cleaned)
+        out.positions = np.zeros(n_sel, np.uint32)
+        out.model = np.zeros((n, n_sel), np.float32)
+        out.trace = np.zeros((n_tr, 2), np.uint32)
+        out.margins = np.zeros(n_tr + 1, np.float32)
+        out.values = np.zeros(n_tr + 1, np.float32)
+        L.orc_subminor_fetch(handle, out.positions.ctypes.data, out.model.ctypes.data,
+                             out.trace.ctypes.data, out.margins.ctypes.data,
+                             out.values.ctypes.data)
+        L.orc_subminor_free(handle)
         return out
 
     def integrate(self, images, weights=None, n_pol=1, pol_factor=1.0, square=False,
