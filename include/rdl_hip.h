@@ -492,7 +492,15 @@ typedef struct {
  * (cpp/algorithms/generic_clean.cc:163-207): per iteration gather N_img peak
  * values, model += gain*v, subtract PSF_i, square-integrate, find peak,
  * divergence test. The loop runs device-resident; h_trace (may be NULL)
- * receives x,y per component (2 x uint32 each, up to trace_cap). */
+ * receives x,y per component (2 x uint32 each, up to trace_cap). Index 0 of
+ * h_trace is the first component of this call, whatever iteration_start is;
+ * entries past min(components of this call, trace_cap) are left untouched,
+ * and so is all of it when trace_cap is 0.
+ * out->iteration counts on from iteration_start. When the loop ends with
+ * out->found = 0 (a mask, and a search that met no qualifying pixel inside
+ * it), out->peak, x and y are those of the last peak that was found: the
+ * last component's, or the start peak's when no component was taken
+ * (start_found = 0: p's own start values). */
 int rdl_hogbom_run(rdl_session* s, float* d_residuals, float* d_models,
                    const float* d_psfs, const rdl_hogbom_params* p,
                    rdl_hogbom_result* out, uint32_t* h_trace,

@@ -171,6 +171,8 @@ struct OrcAlgo {
   int component_optimization = 0;    // SetComponentOptimizationAlgorithm
   std::vector<float> margins;        // decision margins of the last trace (+ end)
   std::vector<float> values;         // the components' |peak| (+ the last one)
+  std::vector<float> spectral_map;   // orc_algo_set_spectral_map (empty = none)
+  size_t spectral_map_n = 0;
 };
 
 static AlgoSettings MakeSettings(const orc_algo_settings* a) {
@@ -263,9 +265,14 @@ int orc_algo_execute(void* h, const orc_set_desc* d, float* residual,
     algo->settings.rms_factor = algo->rms_factor.empty() ? nullptr : algo->rms_factor.data();
     algo->settings.component_optimization = algo->component_optimization;
     if (algo->ms) algo->ms->Settings().rms_factor = algo->settings.rms_factor;
+    MarginTracker hogbom_margins;
     if (algo->type == 0) {
-      r = GenericCleanExecute(algo->settings, algo->iteration_number, res, mod,
-                              psf_ptrs, &tr);
+      if (!algo->spectral_map.empty() && algo->spectral_map_n != res.Size())
+        throw std::runtime_error("spectral map does not match the image count");
+      r = GenericCleanExecute(
+          algo->settings, algo->iteration_number, res, mod, psf_ptrs, &tr,
+          algo->spectral_map.empty() ? nullptr : algo->spectral_map.data(),
+          &hogbom_margins);
     } else if (algo->type == 2) {
       // IuwtDeconvolution::ExecuteMajorIteration (iuwt_deconvolution.h:22-39)
       IuwtAlgoSettings is;
@@ -298,8 +305,7 @@ int orc_algo_execute(void* h, const orc_set_desc* d, float* residual,
       algo->margins.push_back(c.margin);
       algo->values.push_back(c.value);
     }
-    algo->margins.push_back(algo->ms ? algo->ms->end_margin
-                                     : std::numeric_limits<float>::infinity());
+    algo->margins.push_back(algo->ms ? algo->ms->end_margin : hogbom_margins.Take());
     algo->values.push_back(tr.empty() ? 1.0f : tr.back().value);
     if (trace) {
       const size_t n = std::min<size_t>(tr.size(), trace_cap);
@@ -443,6 +449,18 @@ void orc_algo_set_rms(void* h, const float* factor, uint64_t n) {
     algo->rms_factor.assign(factor, factor + n);
   else
     algo->rms_factor.clear();
+}
+
+// A spectral map for the Högbom branch of GenericClean (type 0 without the
+// sub-minor loop) in place of PerformSpectralFit: n x n row-major floats, n the
+// image count (oracle.h GenericCleanExecute); NULL clears it.
+void orc_algo_set_spectral_map(void* h, const float* map, uint64_t n) {
+  auto* algo = static_cast<OrcAlgo*>(h);
+  if (map)
+    algo->spectral_map.assign(map, map + n * n);
+  else
+    algo->spectral_map.clear();
+  algo->spectral_map_n = map ? n : 0;
 }
 
 // DeconvolutionAlgorithm::SetComponentOptimizationAlgorithm (0 clean, 2 gradient

@@ -643,8 +643,33 @@ void SubMinorLoop::CorrectResidualDirty(size_t image_index, float* residual,
 // GenericClean — cpp/algorithms/generic_clean.cc:56-277
 // ---------------------------------------------------------------------------
 namespace {
+// The gap between the value that won a peak search and the runner-up: the
+// largest value among the other pixels the search looks at (inside the
+// border box and the mask, NaN never compares greater).
+void NotePeakMargin(const AlgoSettings& s, const float* image, size_t w, size_t h,
+                    size_t hb, size_t vb, const Peak& peak, MarginTracker& margins) {
+  const auto value = [&](size_t i) {
+    return s.allow_negative ? std::fabs(image[i]) : image[i];
+  };
+  size_t xs, xe, ys, ye;
+  Box(w, h, 0, h, hb, vb, xs, xe, ys, ye);
+  const size_t chosen = peak.x + peak.y * w;
+  bool any = false;
+  float second = 0.0f;
+  for (size_t y = ys; y != ye; ++y)
+    for (size_t x = xs; x != xe; ++x) {
+      const size_t i = y * w + x;
+      if (i == chosen || (s.clean_mask && !s.clean_mask[i])) continue;
+      if (!any ? value(i) == value(i) : value(i) > second) {
+        second = value(i);
+        any = true;
+      }
+    }
+  if (any) margins.Note(value(chosen), second);
+}
+
 Peak GenericFindPeak(const AlgoSettings& s, const float* image, size_t w,
-                     size_t h) {
+                     size_t h, MarginTracker* margins = nullptr) {
   // generic_clean.cc:255-277 via peak_finder.h:99-107 (border by round())
   const size_t hb = std::round(w * s.clean_border_ratio);
   const size_t vb = std::round(h * s.clean_border_ratio);
@@ -654,17 +679,20 @@ Peak GenericFindPeak(const AlgoSettings& s, const float* image, size_t w,
     for (size_t i = 0; i != w * h; ++i) scratch[i] *= s.rms_factor[i];
     image = scratch.data();
   }
-  if (!s.clean_mask)
-    return FindPeakAvx(image, w, h, s.allow_negative, 0, h, hb, vb);
-  return FindPeakWithMask(image, w, h, s.allow_negative, 0, h, s.clean_mask,
-                          hb, vb);
+  const Peak peak =
+      s.clean_mask ? FindPeakWithMask(image, w, h, s.allow_negative, 0, h,
+                                      s.clean_mask, hb, vb)
+                   : FindPeakAvx(image, w, h, s.allow_negative, 0, h, hb, vb);
+  if (margins && peak.has) NotePeakMargin(s, image, w, h, hb, vb, peak, *margins);
+  return peak;
 }
 }  // namespace
 
 Result GenericCleanExecute(const AlgoSettings& s_in, size_t& iteration_number,
                            ImageSet& dirty, ImageSet& model,
                            const std::vector<const float*>& psfs,
-                           std::vector<Component>* trace) {
+                           std::vector<Component>* trace,
+                           const float* spectral_map, MarginTracker* margins) {
   AlgoSettings s = s_in;
   const size_t width = dirty.width, height = dirty.height;
   const size_t start_iter = iteration_number;
@@ -676,7 +704,11 @@ Result GenericCleanExecute(const AlgoSettings& s_in, size_t& iteration_number,
 
   std::vector<float> integrated(width * height);
   GetLinearIntegrated(dirty, integrated.data());
-  Peak max_value = GenericFindPeak(s, integrated.data(), width, height);
+  // (the margins are the Högbom branch's alone)
+  MarginTracker* const hogbom_margins =
+      s.use_sub_minor_optimization ? nullptr : margins;
+  Peak max_value =
+      GenericFindPeak(s, integrated.data(), width, height, hogbom_margins);
   Result result;
   result.has_starting_peak = max_value.has;
   result.starting_peak = max_value.value;
@@ -743,17 +775,35 @@ Result GenericCleanExecute(const AlgoSettings& s_in, size_t& iteration_number,
     }
   } else {
     size_t peak_index = max_value.x + max_value.y * width;
-    std::vector<float> peak_values(dirty.Size());
-    while (max_value.has && std::fabs(max_value.value) > first_threshold &&
-           iteration_number < s.max_iterations &&
-           !(max_value.value < 0.0f && s.stop_on_negative) && !diverging) {
+    const size_t n_img = dirty.Size();
+    std::vector<float> peak_values(n_img), mapped(n_img);
+    for (;;) {
+      if (margins && max_value.has)
+        margins->Note(std::fabs(max_value.value), first_threshold);
+      if (!(max_value.has && std::fabs(max_value.value) > first_threshold &&
+            iteration_number < s.max_iterations &&
+            !(max_value.value < 0.0f && s.stop_on_negative) && !diverging))
+        break;
       if (trace)
         trace->push_back({uint32_t(peak_index % width),
-                          uint32_t(peak_index / width), 0});
-      for (size_t i = 0; i != dirty.Size(); ++i)
+                          uint32_t(peak_index / width), 0,
+                          margins ? margins->Take()
+                                  : std::numeric_limits<float>::infinity(),
+                          std::fabs(max_value.value)});
+      for (size_t i = 0; i != n_img; ++i)
         peak_values[i] = dirty.images[i][peak_index];
-      PerformSpectralFit(dirty.desc->fitter.get(), dirty.desc->n_pol,
-                         peak_values.data());  // generic_clean.cc:186
+      if (spectral_map) {
+        for (size_t i = 0; i != n_img; ++i) {
+          float acc = 0.0f;
+          for (size_t q = 0; q != n_img; ++q)
+            acc = std::fmaf(spectral_map[i * n_img + q], peak_values[q], acc);
+          mapped[i] = acc;
+        }
+        peak_values = mapped;
+      } else {
+        PerformSpectralFit(dirty.desc->fitter.get(), dirty.desc->n_pol,
+                           peak_values.data());  // generic_clean.cc:186
+      }
       const size_t cx = peak_index % width, cy = peak_index / width;
       for (size_t i = 0; i != dirty.Size(); ++i) {
         peak_values[i] *= s.minor_loop_gain;
@@ -762,11 +812,15 @@ Result GenericCleanExecute(const AlgoSettings& s_in, size_t& iteration_number,
                       cx, cy, peak_values[i]);
       }
       GetSquareIntegrated(dirty, integrated.data());
-      max_value = GenericFindPeak(s, integrated.data(), width, height);
+      max_value = GenericFindPeak(s, integrated.data(), width, height, margins);
       peak_index = max_value.x + max_value.y * width;
-      if (max_value.has && s.divergence_limit != 0.0f)
+      if (max_value.has && s.divergence_limit != 0.0f) {
+        if (margins)
+          margins->Note(std::fabs(max_value.value),
+                        initial_max_value * s.divergence_limit);
         diverging =
             std::fabs(max_value.value) > initial_max_value * s.divergence_limit;
+      }
       ++iteration_number;
     }
   }

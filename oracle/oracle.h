@@ -228,10 +228,21 @@ class SubMinorLoop {
 };
 
 // cpp/algorithms/generic_clean.cc:56-253
+// Tests only, both for the Högbom branch (use_sub_minor_optimization off):
+// spectral_map is an n_img x n_img row-major float map applied to the
+// gathered peak values in place of PerformSpectralFit, before the gain:
+// f[i] = (sum over q ascending of fmaf(S[i][q], r[q], acc), acc from 0) * gain,
+// in float (the C-ABI's definition of rdl_hogbom_params::d_spectral);
+// margins receives the decision margins: the runner-up gap of every peak
+// search and the loop-continue comparisons go into the trace's
+// Component::margin, and what is pending at the return is the margin of the
+// decisions that ended the run.
 Result GenericCleanExecute(const AlgoSettings& s, size_t& iteration_number,
                            ImageSet& dirty, ImageSet& model,
                            const std::vector<const float*>& psfs,
-                           std::vector<Component>* trace);
+                           std::vector<Component>* trace,
+                           const float* spectral_map = nullptr,
+                           MarginTracker* margins = nullptr);
 
 // cpp/algorithms/multiscale_algorithm.cc
 struct ScaleInfo {

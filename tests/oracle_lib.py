@@ -451,15 +451,30 @@ class OracleAlgorithm:
             f = np.ascontiguousarray(factor, np.float32)
             L.orc_algo_set_rms(self.h, f.ctypes.data, f.size)
 
+    def set_spectral_map(self, smap):
+        """An n_img x n_img float map in place of PerformSpectralFit in the
+        Högbom branch of GenericClean (kind 0, use_sub_minor=0), applied as
+        rdl_hogbom_params::d_spectral is defined (None clears it)."""
+        L = self.o.lib
+        L.orc_algo_set_spectral_map.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.orc_algo_set_spectral_map.restype = None
+        if smap is None:
+            L.orc_algo_set_spectral_map(self.h, None, 0)
+        else:
+            m = np.ascontiguousarray(smap, np.float32)
+            assert m.ndim == 2 and m.shape[0] == m.shape[1]
+            L.orc_algo_set_spectral_map(self.h, m.ctypes.data, m.shape[0])
+
     def update(self, **settings):
         self.settings = algo_settings(**settings)
         self.o.lib.orc_algo_update(self.h, C.byref(self.settings))
 
-    def execute(self, residual, model, psfs, weights=None, trace_cap=1 << 22):
+    def execute(self, residual, model, psfs, weights=None, trace_cap=1 << 22, pol_factor=1.0,
+                squared_joins=False):
         """residual/model: (n_img, h, w) float32 updated in place; psfs (n_ch, h, w)."""
         n, h, w = residual.shape
-        d = Oracle.set_desc(w, h, psfs.shape[0], n // psfs.shape[0], weights,
-                            spectral=self.spectral)
+        d = Oracle.set_desc(w, h, psfs.shape[0], n // psfs.shape[0], weights, pol_factor,
+                            squared_joins, spectral=self.spectral)
         r = Result()
         trace = np.zeros((trace_cap, 3), np.uint32)
         rc = self.o.lib.orc_algo_execute(self.h, C.byref(d), residual, model,
@@ -472,7 +487,9 @@ class OracleAlgorithm:
     def margins(self):
         """Decision margins of the last execute (oracle.h Component::margin):
         (margins [n_trace + 1], values [n_trace + 1]); the last entry is the
-        end-of-run margin and the last component's |peak|."""
+        end-of-run margin and the last component's |peak|. Recorded by the
+        multiscale algorithm and by GenericClean's Högbom branch
+        (use_sub_minor=0); infinite otherwise."""
         L = self.o.lib
         L.orc_algo_margins.restype = C.c_uint64
         L.orc_algo_margins.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]

@@ -114,6 +114,19 @@ def logpoly(frequencies, weights, n_terms):
     return lp
 
 
+class ForcedTerms(C.Structure):
+    """rdl_forced_terms (include/rdl_hip.h)."""
+    _fields_ = [("d_planes", C.c_void_p), ("plane_stride", C.c_size_t),
+                ("pitch", C.c_uint32), ("rows", C.c_uint32),
+                ("x0", C.c_uint32), ("y0", C.c_uint32),
+                ("weights", C.c_float * 16)]
+
+
+class ForcedLogPoly(C.Structure):
+    """rdl_forced_logpoly."""
+    _fields_ = [("fit", LogPoly), ("terms", ForcedTerms)]
+
+
 class RdlError(RuntimeError):
     pass
 

@@ -7,10 +7,13 @@
 * convolution: against numpy float64 FFT (schaapcommon::math::Convolve is absent:
   its contract is restated from call sites, see oracle/fft.h)
 * end-to-end: cpp/test/test_radler.cc:106-172 point-source cases at algorithm level
+* the Högbom branch's spectral map and decision margins (test harness only):
+  against no fitting, the polynomial fitter and a float32 numpy restatement
 """
 import numpy as np
 import pytest
 
+from hogbom_cases import mixed, numpy_hogbom_map_loop, single
 from oracle_lib import OracleAlgorithm, get_oracle, get_ref
 
 
@@ -204,3 +207,94 @@ def test_point_source(orc, kind, use_sub_minor, shift):
     m[cy, cx] = 0
     assert np.abs(m).max() < 2e-6
     assert tuple(trace[0, :2]) == (cx, cy)
+
+
+# ---------------------------------------------------------------- Högbom map
+# The Högbom branch's spectral map and decision margins (oracle.h
+# GenericCleanExecute), which tests/test_hogbom_options_gpu.py relies on.
+def _hogbom(orc, dirties, psfs, n_it, smap=None, fitter=None, weights=None):
+    res, mod = np.array(dirties, np.float32), np.zeros(dirties.shape, np.float32)
+    alg = OracleAlgorithm(orc, 0, threshold=0.0, max_iterations=n_it, border_ratio=0.0,
+                          use_sub_minor=0, divergence_limit=0.0)
+    alg.set_spectral_map(smap)
+    if fitter is not None:
+        alg.set_spectral_fitter(*fitter)
+    r, trace = alg.execute(res, mod, np.ascontiguousarray(psfs), weights)
+    return r, trace[:, :2], res, mod, alg
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("n_img", [1, 4])
+def test_hogbom_identity_map_is_no_fitting(orc, n_img):
+    dirties, psfs = single(64, 48) if n_img == 1 else mixed(64, 48, n_img)
+    r0, t0, res0, mod0, _ = _hogbom(orc, dirties, psfs, 60)
+    r1, t1, res1, mod1, _ = _hogbom(orc, dirties, psfs, 60, smap=np.eye(n_img, dtype=np.float32))
+    assert r0.iteration_number == r1.iteration_number == 60 and len(set(map(tuple, t0))) >= 8
+    assert np.array_equal(t0, t1)
+    assert np.array_equal(_bits(res0), _bits(res1)) and np.array_equal(_bits(mod0), _bits(mod1))
+    assert _bits(r0.final_peak) == _bits(r1.final_peak)
+
+
+def test_hogbom_map_of_the_polynomial_fitter(orc):
+    """The polynomial fitter is linear: the map whose columns are its
+    responses to the unit vectors gives the fitter's trace, and its planes
+    within test_spectral.py's bound for a fitter restated another way."""
+    n_ch, terms = 4, 2
+    freqs, wts = 1.0e8 * 1.25 ** np.arange(n_ch), np.array([1.0, 0.5, 2.0, 1.0], np.float32)
+    smap = np.stack([orc.spectral_fit(1, terms, freqs, wts, e)[0]
+                     for e in np.eye(n_ch, dtype=np.float32)], axis=1)
+    assert not np.array_equal(smap, smap.T) and not np.array_equal(smap, np.eye(n_ch))
+    dirties, psfs = mixed(64, 48, n_ch)
+    join = None  # uniform, not the fit's weights: the integrated peak then moves with the fit
+    rf, tf, resf, modf, _ = _hogbom(orc, dirties, psfs, 60, fitter=(1, terms, freqs, wts),
+                                    weights=join)
+    rm, tm, resm, modm, alg = _hogbom(orc, dirties, psfs, 60, smap=smap, weights=join)
+    _, t0, _, mod0, _ = _hogbom(orc, dirties, psfs, 60, weights=join)
+    assert not np.array_equal(t0, tm) and not np.array_equal(mod0, modm)  # the map does something
+    margins, values = alg.margins()
+    assert float(np.min(margins / values)) >= 1e-4  # no decision the two forms could take apart
+    assert np.array_equal(tf, tm)
+    tol = 2e-5 * float(np.abs(dirties).max())
+    assert np.abs(resf - resm).max() <= tol and np.abs(modf - modm).max() <= tol
+    assert abs(float(rf.final_peak) - float(rm.final_peak)) <= tol
+
+
+def test_hogbom_margins(orc):
+    """One margin per component and one for the end of the run, each the
+    smallest gap of the decisions behind it: positive, finite, and no larger
+    than the |peak| - threshold comparison that lets the loop go on."""
+    dirties, psfs = single(96, 80)
+    thr = 0.3 * float(np.abs(dirties).max())
+    res, mod = dirties.copy(), np.zeros_like(dirties)
+    alg = OracleAlgorithm(orc, 0, threshold=thr, max_iterations=400, border_ratio=0.0,
+                          use_sub_minor=0)
+    r, trace = alg.execute(res, mod, psfs)
+    margins, values = alg.margins()
+    assert 10 < r.iteration_number < 400 and len(margins) == len(trace) + 1
+    assert np.all(np.isfinite(margins)) and np.all(margins > 0) and np.all(values > 0)
+    assert np.all(margins[:-1] <= values[:-1] - np.float32(thr))
+    assert margins[-1] <= np.float32(thr) - abs(r.final_peak)
+    # the first component's margin: the runner-up gap of the first search
+    first = np.sort(np.abs(dirties[0]).ravel())[-2:]
+    assert margins[0] == min(first[1] - first[0], first[1] - np.float32(thr))
+    # with the sub-minor loop the algorithm object reports none
+    alg = OracleAlgorithm(orc, 0, threshold=thr, max_iterations=400, border_ratio=0.0)
+    alg.execute(dirties.copy(), np.zeros_like(dirties), psfs)
+    assert np.all(np.isinf(alg.margins()[0]))
+
+
+def test_hogbom_map_matches_numpy_restatement(orc):
+    """The oracle's map form against the loop written out in float32 numpy
+    (hogbom_cases.numpy_hogbom_map_loop), bit for bit on 3 channels."""
+    dirties, psfs = mixed(61, 47, 3)
+    wts = np.array([1.0, 0.5, 2.0], np.float32)
+    smap = np.array([[0.8, 0.3, -0.1], [0.25, 0.5, 0.25], [-0.2, 0.4, 0.9]], np.float32)
+    r, trace, res, mod, _ = _hogbom(orc, dirties, psfs, 50, smap=smap, weights=wts)
+    t_np, res_np, mod_np, peak_np = numpy_hogbom_map_loop(dirties, psfs, wts, smap, 0.0, 0.1, 50)
+    assert r.iteration_number == 50 and len(set(map(tuple, trace))) >= 8
+    assert np.array_equal(trace, t_np)
+    assert np.array_equal(_bits(res), _bits(res_np)) and np.array_equal(_bits(mod), _bits(mod_np))
+    assert _bits(r.final_peak) == _bits(peak_np)

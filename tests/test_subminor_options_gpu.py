@@ -33,7 +33,8 @@ import numpy as np
 import pytest
 
 from oracle_lib import get_oracle
-from rdl_lib import LogPoly, Session, SubminorParams, SubminorResult, integration, logpoly
+from rdl_lib import (ForcedLogPoly, Session, SubminorParams, SubminorResult, integration,
+                     logpoly)
 from subminor_cases import joined, synthetic
 from test_subminor_plan import _host_build
 
@@ -42,19 +43,6 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 KIND_NAMES = ["Lds", "Reg", "Wave", "Big", "Tab", "TabN"]  # rdl::LoopKind
 LOGPOLY = 2  # oracle/spectral.h SpectralFit::mode
-
-
-class ForcedTerms(C.Structure):
-    """rdl_forced_terms (include/rdl_hip.h)."""
-    _fields_ = [("d_planes", C.c_void_p), ("plane_stride", C.c_size_t),
-                ("pitch", C.c_uint32), ("rows", C.c_uint32),
-                ("x0", C.c_uint32), ("y0", C.c_uint32),
-                ("weights", C.c_float * 16)]
-
-
-class ForcedLogPoly(C.Structure):
-    """rdl_forced_logpoly."""
-    _fields_ = [("fit", LogPoly), ("terms", ForcedTerms)]
 
 
 def bits(a):
