@@ -1,7 +1,8 @@
 // What the sub-minor loop's translation units share: the handle, the loop
 // kernels' arguments and result, the argmax key, the write-through and
 // cross-lane helpers, and the host functions each unit offers the others
-// (subminor.hip holds the sequence that calls them).
+// (subminor.hip holds the sequence that calls them). The device functions
+// that only the loop kernels share are in subminor_loop_shared.h.
 #pragma once
 #include <cmath>
 #include <cstdio>

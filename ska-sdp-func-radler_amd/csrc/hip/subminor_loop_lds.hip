@@ -10,7 +10,8 @@
 // re-integrates and reduces its argmax; with G > 1 the winners are exchanged
 // through write-through (sc1) records and a monotonic arrival counter, so all
 // workgroups take the same next component.
-#include "subminor_internal.h"
+// From subminor_loop_shared.h: WriteTrace and WriteResult.
+#include "subminor_loop_shared.h"
 
 namespace rdl {
 
@@ -279,13 +280,9 @@ __global__ __launch_bounds__(kLoopThreads) void SubminorLoop(LoopArgs a) {
           if (k < int(n_img)) M[k * stride + j] += c[k];
       }
     }
-    if (blockIdx.x == 0 && tid == 0 && a.trace) {
-      const uint64_t t = iteration - a.iteration_start;
-      if (t < a.trace_cap) {
-        a.trace[2 * t] = uint32_t(cx);
-        a.trace[2 * t + 1] = uint32_t(cy);
-      }
-    }
+    if (blockIdx.x == 0 && tid == 0 && a.trace)
+      WriteTrace(a.trace, a.trace_cap, iteration - a.iteration_start, uint32_t(cx),
+                 uint32_t(cy));
     have_component = true;
     __syncthreads();
   }
@@ -296,13 +293,7 @@ __global__ __launch_bounds__(kLoopThreads) void SubminorLoop(LoopArgs a) {
       for (uint32_t k = 0; k < n_img; ++k)
         a.m[size_t(k) * a.n_sel + base + j] = M[k * stride + j];
   }
-  if (blockIdx.x == 0 && tid == 0) {
-    LoopResult* r = reinterpret_cast<LoopResult*>(a.result);
-    r->iteration = iteration;
-    r->peak = m;
-    r->diverging = diverging ? 1 : 0;
-    r->flux = flux;
-  }
+  if (blockIdx.x == 0 && tid == 0) WriteResult(a.result, iteration, m, diverging, flux);
 }
 
 template <int NI>

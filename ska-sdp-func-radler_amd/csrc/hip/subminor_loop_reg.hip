@@ -9,9 +9,10 @@
 // sweeps all G records until every tag matches, so the data is the flag and
 // no counter or fence round trip is needed (parity-double-buffered so a fast
 // block never overwrites a record a slow one has not read).
+// From subminor_loop_shared.h: WriteTrace and WriteResult.
 #include <type_traits>
 
-#include "subminor_internal.h"
+#include "subminor_loop_shared.h"
 
 namespace rdl {
 
@@ -465,13 +466,9 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopReg(LoopArgs a) {
             for (int k = 0; k < NI; ++k) M[i][k] += c[k];
       }
     }
-    if (blockIdx.x == 0 && tid == 0 && a.trace) {
-      const uint64_t t = iteration - a.iteration_start;
-      if (t < a.trace_cap) {
-        a.trace[2 * t] = uint32_t(cx);
-        a.trace[2 * t + 1] = uint32_t(cy);
-      }
-    }
+    if (blockIdx.x == 0 && tid == 0 && a.trace)
+      WriteTrace(a.trace, a.trace_cap, iteration - a.iteration_start, uint32_t(cx),
+                 uint32_t(cy));
     have_component = true;
     RDL_PHASE(5)
   }
@@ -489,13 +486,7 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopReg(LoopArgs a) {
       for (int k = 0; k < NI; ++k)
         if (k < n_img) a.m[size_t(k) * a.n_sel + base + j] = M[i][k];
   }
-  if (blockIdx.x == 0 && tid == 0) {
-    LoopResult* r = reinterpret_cast<LoopResult*>(a.result);
-    r->iteration = iteration;
-    r->peak = m;
-    r->diverging = diverging ? 1 : 0;
-    r->flux = flux;
-  }
+  if (blockIdx.x == 0 && tid == 0) WriteResult(a.result, iteration, m, diverging, flux);
 }
 
 // THREADS = 64: the single wave; 512; 1024: one sixteen-wave workgroup (or a

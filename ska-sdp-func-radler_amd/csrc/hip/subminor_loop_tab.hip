@@ -1,7 +1,10 @@
 // The sub-minor loops that read the pairwise PSF table, and the table's
 // builder: SubminorLoopTab (one image, the multiscale hot path) and
-// SubminorLoopTabN (joined images).
-#include "subminor_internal.h"
+// SubminorLoopTabN (joined images). From subminor_loop_shared.h: the
+// per-thread best by |value| (ThreadBestAbs), the (hi, lo) winner among lanes
+// (LexMaxLane), the participants' handshake (XccHandshake, with the note on
+// why the fast exchange is sound), WriteTrace and WriteResult.
+#include "subminor_loop_shared.h"
 
 namespace rdl {
 
@@ -60,26 +63,6 @@ __global__ __launch_bounds__(256) void BuildPairTable(const uint32_t* __restrict
 //
 // Same operations in the same order, same argmax order and tie rules as the
 // generic kernels: traces and model values are identical.
-
-// The "fast" exchange below publishes records with workgroup-scope stores
-// that the other participants poll with agent-scope (L1-bypassing) loads:
-// visible to them only because gfx950's vector L1 is write-through, so every
-// store reaches the XCD's L2 the participants share (checked at run time:
-// all participants on one XCC). A target whose L1 could hold such stores
-// needs the agent-scope form, which RDL_SUBMINOR_EXCHANGE=agent selects (and
-// tests/test_gpu_kernels.py compares with the fast one).
-// Other targets always take the agent-scope form (kFastExchange false).
-#if defined(__gfx950__) || !defined(__HIP_DEVICE_COMPILE__)
-constexpr bool kFastExchange = true;
-#else
-constexpr bool kFastExchange = false;
-#endif
-
-__device__ __forceinline__ uint32_t XccId() {
-  // HW_REG_XCC_ID (hwreg 20), bits [3:0]
-  return uint32_t(__builtin_amdgcn_s_getreg((20) | (0 << 6) | ((4 - 1) << 11)));
-}
-
 template <int ITEMS, int THREADS, bool NEG>
 __global__ __launch_bounds__(THREADS) void SubminorLoopTab(LoopArgs a) {
   constexpr int WAVES = THREADS / 64;
@@ -114,29 +97,13 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTab(LoopArgs a) {
   bool fast = true;  // G > 1: exchange through the one L2 of the participants
   bool failed = false;
   if (G > 1) {
-    if (tid == 0)
-      __hip_atomic_store(gran + rank, (uint64_t(1) << 32) | XccId(), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t xcc = 0u;
-    bool ok = false;
-    for (uint64_t spins = 0; !failed; ++spins) {
-      uint64_t v = 0;
-      if (lane < G)
-        v = __hip_atomic_load(gran + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      ok = lane >= G || (v >> 32) == 1u;
-      if (__all(ok)) {
-        xcc = uint32_t(v);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-      failed = spins > (uint64_t(1) << 24);
-    }
-    const uint32_t x0 = uint32_t(__builtin_amdgcn_readlane(int(xcc), 0));
-    fast = kFastExchange && __all(lane >= G || xcc == x0) && !a.agent_exchange;
+    const Handshake hs = XccHandshake(gran, G, rank, lane, tid, a.agent_exchange != 0);
+    fast = hs.fast;
+    failed = hs.failed;
   }
   const float* table = a.table;
   float c = 0.0f, m = 0.0f, start_abs = 0.0f, flux = 0.0f;
-  uint32_t cp = 0, par = 0, epoch = 0;
+  uint32_t par = 0, epoch = 0;
   uint32_t row_cp = 0xffffffffu;  // the component whose row pv holds
   float pv[ITEMS];
   uint32_t pend_pos = 0;
@@ -179,37 +146,22 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTab(LoopArgs a) {
       for (int i = 0; i < ITEMS; ++i)
         if (__float_as_uint(pv[i]) != kOutsideBits) R[i] = __builtin_fmaf(-pv[i], c, R[i]);
       if (pend) {  // the previous component's position has arrived with the row
-        const uint64_t t = iteration - a.iteration_start;
-        if (t < a.trace_cap) {
-          a.trace[2 * t] = pend_pos & 0xffffu;
-          a.trace[2 * t + 1] = pend_pos >> 16;
-        }
+        WriteTrace(a.trace, a.trace_cap, iteration - a.iteration_start, pend_pos & 0xffffu,
+                   pend_pos >> 16);
         pend = false;
       }
     }
     RDL_TPHASE(0)
     // ---- this thread's best: the largest key, then the lowest index
-    // (MaxKey's high word; NaN 0, index 0's NaN ~0); compares and selects
-    // only, no branch per item
     uint32_t bh = 0u, bj = 0xffffffffu, bv = __float_as_uint(R[0]);
     if constexpr (NEG) {
-      // |R| keys: the largest |R| by a float max chain (the max skips NaN,
-      // whose key is 0), then the lowest item holding it
-      float tb = -1.0f;
-#pragma unroll
-      for (int i = 0; i < ITEMS; ++i) tb = __builtin_fmaxf(tb, __builtin_fabsf(R[i]));
-      bh = tb >= 0.0f ? (__float_as_uint(tb) | 0x80000000u) : 0u;
-#pragma unroll
-      for (int i = ITEMS - 1; i >= 0; --i) {
-        const bool eq = __builtin_fabsf(R[i]) == tb;
-        bj = eq ? base + tid + uint32_t(i) * THREADS : bj;
-        bv = eq ? __float_as_uint(R[i]) : bv;
-      }
-      if (base == 0u && tid == 0u && cnt > 0u && R[0] != R[0]) {
-        bh = 0xffffffffu;  // selection index 0 holding NaN outranks every key
-        bj = 0u;
-      }
+      const ThreadWinner best = ThreadBestAbs<ITEMS, THREADS>(R, base, tid, cnt);
+      bh = best.bh;
+      bj = best.bj;
+      bv = best.bv;
     } else {
+      // the general form (ThreadBestAbs's rule on MaxKey's high word of R or
+      // |R|; spelled out here and in SubminorLoopTabN)
 #pragma unroll
       for (int i = 0; i < ITEMS; ++i) {
         const float v = neg ? fabsf(R[i]) : R[i];
@@ -267,15 +219,9 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTab(LoopArgs a) {
       }
     } else {
     // ---- wave winner: DPP max of the keys; the lowest index on exact ties
-    const uint32_t mh = MaxU32<64>(bh);
-    const uint64_t tie = __ballot(bh == mh);
-    int owner;
-    if ((tie & (tie - 1ull)) == 0ull) {
-      owner = __builtin_ctzll(tie);
-    } else {  // several lanes: the largest ~j among them (0: a key-0 wave)
-      const uint32_t ml = MaxU32<64>(bh == mh ? ~bj : 0u);
-      owner = FirstLane(bh == mh && ~bj == ml);
-    }
+    const LaneWinner ww = LexMaxLane<64>(bh, ~bj, true);
+    const uint32_t mh = ww.hi;
+    int owner = ww.lane;
     // a key-0 wave stands for its first pixel (lane 0's item 0, as
     // SubminorLoopReg), whose value is lane 0's initial bv
     const uint32_t wl = mh == 0u ? 0u : ~uint32_t(__builtin_amdgcn_readlane(int(bj), owner));
@@ -287,18 +233,10 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTab(LoopArgs a) {
     // ---- block winner over the wave slots
     const uint4 s4 = lane < uint32_t(WAVES) ? slots[par][lane] : make_uint4(0u, 0u, 0u, 0u);
     par ^= 1u;
-    gh = MaxU32<SLANES>(s4.x);
     {
-      const bool mine = lane < uint32_t(WAVES) && s4.x == gh;
-      const uint64_t t2 = __ballot(mine);
-      int win;
-      if ((t2 & (t2 - 1ull)) == 0ull) {
-        win = __builtin_ctzll(t2);
-      } else {
-        const uint32_t l2 = MaxU32<SLANES>(mine ? s4.y : 0u);
-        win = FirstLane(mine && s4.y == l2);
-      }
-      owner = win;
+      const LaneWinner bw = LexMaxLane<SLANES>(s4.x, s4.y, lane < uint32_t(WAVES));
+      gh = bw.hi;
+      owner = bw.lane;
     }
     gl = uint32_t(__builtin_amdgcn_readlane(int(s4.y), owner));
     gv = uint32_t(__builtin_amdgcn_readlane(int(s4.z), owner));
@@ -338,16 +276,9 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTab(LoopArgs a) {
       }
       if (failed) break;
       // lexicographic (hi, lo) max over the participants (lanes < G)
-      gh = MaxU32<64>(lane < G ? xh : 0u);
-      const bool mine = lane < G && xh == gh;
-      const uint64_t t2 = __ballot(mine);
-      int win;
-      if ((t2 & (t2 - 1ull)) == 0ull) {
-        win = __builtin_ctzll(t2);
-      } else {
-        const uint32_t l2 = MaxU32<64>(mine ? xl : 0u);
-        win = FirstLane(mine && xl == l2);
-      }
+      const LaneWinner xw = LexMaxLane<64>(xh, xl, lane < G);
+      gh = xw.hi;
+      const int win = xw.lane;
       gl = uint32_t(__builtin_amdgcn_readlane(int(xl), win));
       gv = uint32_t(__builtin_amdgcn_readlane(int(xv), win));
     }
@@ -390,7 +321,6 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTab(LoopArgs a) {
     if (!go) break;
     c = m * a.gain;
     flux += c;  // flux += m * gain (the same product)
-    cp = wp;
     // the owner lane adds the component (scalar branches to its wave and item)
     {
       const uint32_t off = wp - base;
@@ -413,13 +343,9 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTab(LoopArgs a) {
     uint64_t* out = reinterpret_cast<uint64_t*>(a.result + 16);
     for (int i = 0; i < 6; ++i) out[i] = ph[i];
   }
-  if (pend) {
-    const uint64_t t = iteration - a.iteration_start;
-    if (t < a.trace_cap) {
-      a.trace[2 * t] = pend_pos & 0xffffu;
-      a.trace[2 * t + 1] = pend_pos >> 16;
-    }
-  }
+  if (pend)
+    WriteTrace(a.trace, a.trace_cap, iteration - a.iteration_start, pend_pos & 0xffffu,
+               pend_pos >> 16);
   if (failed) {
     if (tid == 0) StoreSc1(&a.result[8], 1u);
     return;
@@ -429,13 +355,7 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTab(LoopArgs a) {
     const uint32_t j = tid + uint32_t(i) * THREADS;
     if (j < cnt) a.m[base + j] = M[i];
   }
-  if (rank == 0 && tid == 0) {
-    LoopResult* r = reinterpret_cast<LoopResult*>(a.result);
-    r->iteration = iteration;
-    r->peak = m;
-    r->diverging = diverging ? 1 : 0;
-    r->flux = flux;
-  }
+  if (rank == 0 && tid == 0) WriteResult(a.result, iteration, m, diverging, flux);
 }
 
 // RegIntegration's RDL_INTEGRATE_LINEAR branch alone (SubminorLoopTabN's
@@ -515,30 +435,16 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTabN(LoopArgs a) {
   bool fast = true;
   bool failed = false;
   if (G > 1) {
-    if (tid == 0)
-      __hip_atomic_store(gran + rank, (uint64_t(1) << 32) | XccId(), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t xcc = 0u;
-    for (uint64_t spins = 0; !failed; ++spins) {
-      uint64_t v = 0;
-      if (lane < G)
-        v = __hip_atomic_load(gran + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (__all(lane >= G || (v >> 32) == 1u)) {
-        xcc = uint32_t(v);
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-      failed = spins > (uint64_t(1) << 24);
-    }
-    const uint32_t x0 = uint32_t(__builtin_amdgcn_readlane(int(xcc), 0));
-    fast = kFastExchange && __all(lane >= G || xcc == x0) && !a.agent_exchange;
+    const Handshake hs = XccHandshake(gran, G, rank, lane, tid, a.agent_exchange != 0);
+    fast = hs.fast;
+    failed = hs.failed;
   }
   const size_t sq = size_t(n) * n;
   float c[NI];
 #pragma unroll
   for (int k = 0; k < NI; ++k) c[k] = 0.0f;
   float m = 0.0f, start_abs = 0.0f, flux = 0.0f;
-  uint32_t cp = 0, par = 0, epoch = 0;
+  uint32_t par = 0, epoch = 0;
   uint32_t row_cp = 0xffffffffu;
   float pv[ITEMS][NI];
   uint32_t pend_pos = 0;
@@ -567,11 +473,8 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTabN(LoopArgs a) {
         }
       }
       if (pend) {
-        const uint64_t t = iteration - a.iteration_start;
-        if (t < a.trace_cap) {
-          a.trace[2 * t] = pend_pos & 0xffffu;
-          a.trace[2 * t + 1] = pend_pos >> 16;
-        }
+        WriteTrace(a.trace, a.trace_cap, iteration - a.iteration_start, pend_pos & 0xffffu,
+                   pend_pos >> 16);
         pend = false;
       }
     }
@@ -581,23 +484,13 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTabN(LoopArgs a) {
     for (int i = 0; i < ITEMS; ++i) iv[i] = ri(R[i]);
     uint32_t bh = 0u, bj = 0xffffffffu, bv = __float_as_uint(iv[0]), li = 0u;
     if constexpr (NEG) {
-      float tb = -1.0f;
-#pragma unroll
-      for (int i = 0; i < ITEMS; ++i) tb = __builtin_fmaxf(tb, __builtin_fabsf(iv[i]));
-      bh = tb >= 0.0f ? (__float_as_uint(tb) | 0x80000000u) : 0u;
-#pragma unroll
-      for (int i = ITEMS - 1; i >= 0; --i) {
-        const bool eq = __builtin_fabsf(iv[i]) == tb;
-        bj = eq ? base + tid + uint32_t(i) * THREADS : bj;
-        bv = eq ? __float_as_uint(iv[i]) : bv;
-        li = eq ? uint32_t(i) : li;
-      }
-      if (base == 0u && tid == 0u && cnt > 0u && iv[0] != iv[0]) {
-        bh = 0xffffffffu;
-        bj = 0u;
-        li = 0u;
-      }
+      const ThreadWinner best = ThreadBestAbs<ITEMS, THREADS>(iv, base, tid, cnt);
+      bh = best.bh;
+      bj = best.bj;
+      bv = best.bv;
+      li = best.li;
     } else {
+      // the general form, as SubminorLoopTab's, with the item
 #pragma unroll
       for (int i = 0; i < ITEMS; ++i) {
         const float v = neg ? fabsf(iv[i]) : iv[i];
@@ -612,7 +505,9 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTabN(LoopArgs a) {
         li = better ? uint32_t(i) : li;
       }
     }
-    // ---- wave winner and its image values
+    // ---- wave winner and its image values: LexMaxLane<64>(bh, ~bj, true)
+    // spelled out (called here, next to ThreadBestAbs, it took one VGPR off four
+    // instantiations), with a shortcut for a key-0 wave
     const uint32_t mh = MaxU32<64>(bh);
     const uint64_t tie = __ballot(bh == mh);
     int owner;
@@ -643,17 +538,9 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTabN(LoopArgs a) {
     LdsBarrier();
     // ---- block winner over the wave slots
     const uint4 s4 = lane < uint32_t(WAVES) ? slots[par][lane] : make_uint4(0u, 0u, 0u, 0u);
-    uint32_t gh = MaxU32<SLANES>(s4.x);
-    {
-      const bool mine = lane < uint32_t(WAVES) && s4.x == gh;
-      const uint64_t t2 = __ballot(mine);
-      if ((t2 & (t2 - 1ull)) == 0ull) {
-        owner = __builtin_ctzll(t2);
-      } else {
-        const uint32_t l2 = MaxU32<SLANES>(mine ? s4.y : 0u);
-        owner = FirstLane(mine && s4.y == l2);
-      }
-    }
+    const LaneWinner bw = LexMaxLane<SLANES>(s4.x, s4.y, lane < uint32_t(WAVES));
+    uint32_t gh = bw.hi;
+    owner = bw.lane;
     uint32_t gl = uint32_t(__builtin_amdgcn_readlane(int(s4.y), owner));
     uint32_t gv = uint32_t(__builtin_amdgcn_readlane(int(s4.z), owner));
     float wr[NI];
@@ -698,16 +585,9 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTabN(LoopArgs a) {
         }
       }
       if (failed) break;
-      gh = MaxU32<64>(lane < G ? xr[0] : 0u);
-      const bool mine = lane < G && xr[0] == gh;
-      const uint64_t t2 = __ballot(mine);
-      int win;
-      if ((t2 & (t2 - 1ull)) == 0ull) {
-        win = __builtin_ctzll(t2);
-      } else {
-        const uint32_t l2 = MaxU32<64>(mine ? xr[1] : 0u);
-        win = FirstLane(mine && xr[1] == l2);
-      }
+      const LaneWinner xw = LexMaxLane<64>(xr[0], xr[1], lane < G);
+      gh = xw.hi;
+      const int win = xw.lane;
       gl = uint32_t(__builtin_amdgcn_readlane(int(xr[1]), win));
       gv = uint32_t(__builtin_amdgcn_readlane(int(xr[2]), win));
 #pragma unroll
@@ -752,7 +632,6 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTabN(LoopArgs a) {
       asm volatile("" : "+v"(c[k]));
     }
     flux += m * a.gain;
-    cp = wp;
     {
       const uint32_t off = wp - base;
       if (off < cnt && (off % uint32_t(THREADS)) / 64u == wave) {
@@ -770,13 +649,9 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTabN(LoopArgs a) {
     }
     have = true;
   }
-  if (pend) {
-    const uint64_t t = iteration - a.iteration_start;
-    if (t < a.trace_cap) {
-      a.trace[2 * t] = pend_pos & 0xffffu;
-      a.trace[2 * t + 1] = pend_pos >> 16;
-    }
-  }
+  if (pend)
+    WriteTrace(a.trace, a.trace_cap, iteration - a.iteration_start, pend_pos & 0xffffu,
+               pend_pos >> 16);
   if (failed) {
     if (tid == 0) StoreSc1(&a.result[8], 1u);
     return;
@@ -788,13 +663,7 @@ __global__ __launch_bounds__(THREADS) void SubminorLoopTabN(LoopArgs a) {
 #pragma unroll
       for (int k = 0; k < NI; ++k) a.m[size_t(k) * n + base + j] = M[i][k];
   }
-  if (rank == 0 && tid == 0) {
-    LoopResult* r = reinterpret_cast<LoopResult*>(a.result);
-    r->iteration = iteration;
-    r->peak = m;
-    r->diverging = diverging ? 1 : 0;
-    r->flux = flux;
-  }
+  if (rank == 0 && tid == 0) WriteResult(a.result, iteration, m, diverging, flux);
 }
 
 template <int NI, bool NEG>

@@ -9,7 +9,9 @@ handle in their own copy of the code: RMS-factor weighting, mask and borders
 (every selection mode), allow_negative = 0, stop_on_negative, divergence, the
 iteration window, image sizes with an odd half and a width that is no
 multiple of 4, polarizations and channel weights, the spectral map, and the
-log-polynomial and forced-term fits (Lds only).
+log-polynomial and forced-term fits (Lds only); and for the paths two
+per-run environment switches choose (one-workgroup Tab through the wave slots,
+TabN's grid exchange through agent-scope stores) and exact |value| ties.
 
 One helper (run_case) runs a case on both sides and asserts n_selected, the
 positions, the iteration count, the trace, every image's model values, peak,
@@ -43,6 +45,11 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 KIND_NAMES = ["Lds", "Reg", "Wave", "Big", "Tab", "TabN"]  # rdl::LoopKind
 LOGPOLY = 2  # oracle/spectral.h SpectralFit::mode
+# the grid of images(..., "ties"): the finest power of two at which the
+# oracle's runs of the 256 x 256 images choose a component on an exact tie
+# (2^-12 ... 2^-8 show none: after the first component every pixel the PSF
+# reaches is off the grid)
+TIE_QUANTUM = 2.0 ** -7
 
 
 def bits(a):
@@ -105,7 +112,9 @@ def images(w, h, n_img, n_pol, variant):
     0.6 of its flux, so the largest |value| turns negative after a few
     components; "div": PSFs times -0.5, so subtracting a component grows it;
     "edge": two more sources, 2 pixels from the left edge and 5 from the top
-    (synthetic() keeps its own 8 pixels from every edge)."""
+    (synthetic() keeps its own 8 pixels from every edge); "ties": every value
+    rounded to a multiple of TIE_QUANTUM, both signs, so exact |value| ties
+    occur among the integrated values."""
     psf, dirty = synthetic(w, h, 60, 7)
     if variant == "edge":
         for x, y, flux in ((2, h // 3, 0.8), (w // 3, 5, 0.7)):
@@ -118,6 +127,9 @@ def images(w, h, n_img, n_pol, variant):
         dirties, psfs = joined(dirty, psf, n_img, n_pol)
     if variant == "div":
         psfs = (psfs * np.float32(-0.5)).astype(np.float32)
+    if variant == "ties":
+        dirties = (np.round(dirties / TIE_QUANTUM) * TIE_QUANTUM).astype(np.float32)
+        psfs = (np.round(psfs / TIE_QUANTUM) * TIE_QUANTUM).astype(np.float32)
     dirties.setflags(write=False)
     psfs.setflags(write=False)
     return dirties, psfs
@@ -238,8 +250,17 @@ def device_run(sess, spec):
         cap = max(max_iterations - iteration_start, 1)
         trace = np.full((cap, 2), 0xffffffff, np.uint32)
         dres, dpsf = dev(spec["dirties"]), dev(spec["psfs"])
-        sess.rdl.rdl_subminor_run(sm, dres.vp, dpsf.vp, C.byref(p), C.byref(out),
-                                  trace.ctypes.data_as(C.c_void_p), C.c_uint64(cap))
+        before = {k: os.environ.get(k) for k in spec["env"]}
+        os.environ.update(spec["env"])  # switches rdl_subminor_run reads per run
+        try:
+            sess.rdl.rdl_subminor_run(sm, dres.vp, dpsf.vp, C.byref(p), C.byref(out),
+                                      trace.ctypes.data_as(C.c_void_p), C.c_uint64(cap))
+        finally:
+            for k, v in before.items():
+                if v is None:
+                    del os.environ[k]
+                else:
+                    os.environ[k] = v
         n = int(out.n_selected)
         pos = np.zeros(max(n, 1), np.uint32)
         mod = np.zeros((n_img, max(n, 1)), np.float32)
@@ -256,13 +277,14 @@ def run_case(ctx, kernel, *, w=256, h=256, n_ch=1, n_pol=1, weights=None, pol_fa
              variant="plain", n_sel=None, rms=False, mask=False, h_border=0, v_border=0,
              allow_negative=1, stop_on_negative=0, divergence_limit=4.0, gain=0.1,
              iteration_start=0, max_iterations=300, smap=None, fit=None, table_max=None,
-             select=None, expect=None, custom=None):
+             select=None, expect=None, custom=None, env=None):
     """Runs one case on the device and in the oracle, asserts that they agree
     and that PlanSubminorLoop sends the run to the kernel the case is for.
     kernel: a KERNELS name, or "auto" (mode 0) with expect = (kind, grid,
     build_table). fit: None, ("logpoly", terms) or ("forced",). custom:
     (dirties, psfs, mask, threshold) in place of the generated images and of
-    the threshold that selects about n_sel pixels. Returns the oracle's run
+    the threshold that selects about n_sel pixels. env: environment switches
+    set around rdl_subminor_run alone. Returns the oracle's run
     with .inputs (dirties, psfs, threshold, oracle kwargs) and .plan for the
     caller's preconditions."""
     sess, orc = ctx["sess"], ctx["orc"]
@@ -318,7 +340,7 @@ def run_case(ctx, kernel, *, w=256, h=256, n_ch=1, n_pol=1, weights=None, pol_fa
                 allow_negative=allow_negative, stop_on_negative=stop_on_negative,
                 iteration_start=iteration_start, max_iterations=max_iterations,
                 mask_img=mask_img, rms_img=rms_img, smap=smap, fit=fit, table_max=table_max,
-                select=select)
+                select=select, env=env or {})
     n, pos, mod, out, trace = device_run(sess, spec)
 
     # ---- which kernel ran: PlanSubminorLoop's answer for this launch (an
@@ -619,3 +641,54 @@ def test_product_path(ctx, option, kw, n_sel, kind, table):
     o = run_case(ctx, "auto", n_sel=n_sel, expect=(kind, kind == "Reg", table),
                  table_max=None if table else 0, **kw)
     assert o.plan["kind"] != "TabN" and len(o.trace) >= 20
+
+
+# ------------------------------------------------- paths the options share
+def tie_selection(orc, kernel, n_img=1):
+    """The kernel's selection size, grown to the whole group of equal values
+    its threshold (the n_sel-th largest |integrated value|) falls in on the
+    TIE_QUANTUM grid."""
+    dirties, _ = images(256, 256, n_img, 1, "ties")
+    integ = orc.integrate(dirties, None, 1, 1.0) if n_img > 1 else dirties[0]
+    value = np.sort(np.abs(integ).ravel())
+    return int(np.count_nonzero(value >= value[-KERNELS[kernel][2](n_img)]))
+
+
+def assert_exact_ties(o):
+    """On the oracle alone: some component was chosen with a decision margin
+    of 0, i.e. its runner-up held exactly the same |integrated value|."""
+    assert np.any(o.margins[:len(o.trace)] == 0), float(o.margins[:len(o.trace)].min())
+
+
+@pytest.mark.parametrize("option", ["plain", "positive", "ties"])
+def test_table_wave_slots_one_workgroup(ctx, option):
+    """RDL_SUBMINOR_ATOMIC=0: one-workgroup Tab reduces through the wave
+    slots, the form its grids run, in place of the LDS atomic cells."""
+    kw = dict(plain={}, positive=dict(allow_negative=0, variant="neg"),
+              ties=dict(variant="ties", n_sel=tie_selection(ctx["orc"], "tab1")))[option]
+    o = run_case(ctx, "tab1", env={"RDL_SUBMINOR_ATOMIC": "0"}, **kw)
+    assert len(o.trace) >= 20
+    if option == "ties":
+        assert_exact_ties(o)
+
+
+@pytest.mark.parametrize("n_img", [2, 8])
+def test_joined_table_agent_exchange(ctx, n_img):
+    """RDL_SUBMINOR_EXCHANGE=agent: the grid's records of 3 + n_img granules
+    through agent-scope stores."""
+    o = run_case(ctx, "tabnG", n_ch=n_img, env={"RDL_SUBMINOR_EXCHANGE": "agent"})
+    assert len(o.trace) >= 20
+
+
+TIES = [("tabn1", 2), ("tabn1", 4), ("tabnG", 2), ("tabnG", 4), ("reg1", 1), ("regG", 1)]
+
+
+@pytest.mark.parametrize("kernel,n_img", TIES, ids=[f"{k}-{ni}img" for k, ni in TIES])
+def test_exact_value_ties(ctx, kernel, n_img):
+    """Values on a TIE_QUANTUM grid, both signs: among equal |integrated
+    values| the lowest selection index wins, within a thread, a wave, a
+    workgroup and a grid."""
+    o = run_case(ctx, kernel, n_ch=n_img, variant="ties",
+                 n_sel=tie_selection(ctx["orc"], kernel, n_img))
+    assert len(o.trace) >= 20
+    assert_exact_ties(o)
