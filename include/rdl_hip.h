@@ -1009,6 +1009,41 @@ int rdl_gaussian_weighted_values(rdl_session* s, const float* d_planes, size_t p
                                  const uint32_t* centre_x, const uint32_t* centre_y,
                                  double fwhm_major, double fwhm_minor, double pa, double* out);
 
+/* ------------------------------------------------------- source catalogues */
+/* A whole catalogue of points and sub-pixel elliptical Gaussians drawn into
+ * frequency planes in one call (radler::SourceCatalogue::DrawModel / Restore,
+ * WSClean's -draw-model and -restore-list). Source i is
+ *   g_i(x, y) = exp(-1/2 (qa dx^2 + 2 qb dx dy + qc dy^2)), dx = x - x0, dy = y - y0,
+ * with x the column and y the row index of a pixel, inside its box
+ * |x - round(x0)| <= half_w, |y - round(y0)| <= half_h (round(v) = floor(v + 0.5))
+ * and zero outside it. A point source is qa = qb = qc = 0, half_w = half_h = 0:
+ * its amplitude goes to the one pixel (round(x0), round(y0)), or nowhere when
+ * that pixel lies outside the plane. Centres and boxes may lie outside the
+ * plane; the boxes are clipped to it.
+ *
+ * Contract: for every pixel of every plane g,
+ *   d_planes[g * plane_stride + y * width + x] += float(sum_i amplitude[g][i] g_i(x, y)),
+ * the sum in double over the sources whose box contains the pixel, in ascending
+ * source index, g_i evaluated in double; rounded to float once, then added in
+ * float. A pixel inside no box is not written. No floating-point atomics: a
+ * pixel has one writer, and the result is bitwise reproducible and does not
+ * depend on the tiling or the launch geometry.
+ *
+ * h_shapes and h_amplitudes (n_planes rows of n_sources floats) are host
+ * arrays; the call returns when they have been consumed. n_sources == 0 is a
+ * no-op. RDL_ERR_ARG, before the first device call, for a NULL argument,
+ * n_planes outside 1 .. RDL_MAX_IMAGES, an empty plane, plane_stride <
+ * width * height and a non-finite x0, y0, qa, qb or qc. */
+typedef struct {
+  double x0, y0;           /* centre, fractional pixels (may lie outside the plane) */
+  double qa, qb, qc;       /* g = exp(-1/2 (qa dx^2 + 2 qb dx dy + qc dy^2)) */
+  uint32_t half_w, half_h; /* pixels touched: |ix - round(x0)| <= half_w, same for y */
+} rdl_source_shape;        /* 48 bytes */
+int rdl_draw_sources(rdl_session* s, uint32_t n_sources, const rdl_source_shape* h_shapes,
+                     const float* h_amplitudes /* n_planes rows of n_sources */,
+                     uint32_t n_planes, uint32_t width, uint32_t height,
+                     float* d_planes, size_t plane_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,30 @@ struct ImageCoordinates {
     ra = phase_centre_ra + std::atan2(l, n * cos_dec0 - m * sin_dec0);
     dec = std::asin(m * cos_dec0 + n * sin_dec0);
   }
+  // the inverse of LMToRaDec: the direction cosines of (ra, dec). A direction
+  // on the far hemisphere has the (l, m) of its mirror image: RaDecToN tells
+  template <typename T>
+  static void RaDecToLM(T ra, T dec, T phase_centre_ra, T phase_centre_dec, T& l, T& m) {
+    const T delta = ra - phase_centre_ra;
+    const T cos_dec = std::cos(dec), sin_dec = std::sin(dec);
+    const T cos_dec0 = std::cos(phase_centre_dec), sin_dec0 = std::sin(phase_centre_dec);
+    l = cos_dec * std::sin(delta);
+    m = sin_dec * cos_dec0 - cos_dec * sin_dec0 * std::cos(delta);
+  }
+  // the third direction cosine, negative behind the phase centre
+  template <typename T>
+  static T RaDecToN(T ra, T dec, T phase_centre_ra, T phase_centre_dec) {
+    return std::sin(dec) * std::sin(phase_centre_dec) +
+           std::cos(dec) * std::cos(phase_centre_dec) * std::cos(ra - phase_centre_ra);
+  }
+  // the inverse of XYToLM, fractional: a direction between pixel centres
+  template <typename T>
+  static void LMToXY(T l, T m, T pixel_size_x, T pixel_size_y, size_t width, size_t height,
+                     T& x, T& y) {
+    const T mid_x = T(width) / T(2), mid_y = T(height) / T(2);
+    x = mid_x - l / pixel_size_x;
+    y = mid_y + m / pixel_size_y;
+  }
 };
 
 // aocommon/radeccoord.h, the two formatters the source catalogue uses

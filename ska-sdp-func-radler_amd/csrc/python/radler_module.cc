@@ -21,6 +21,7 @@
 #include "radler.h"
 #include "restore.h"
 #include "rms_image.h"
+#include "source_catalogue.h"
 #include "component_optimization.h"
 #include "fft_sizes.h"
 #include "host_profile.h"
@@ -639,6 +640,207 @@ void InitRestore(py::module& m) {
       },
       py::arg("image"), py::arg("model"), py::arg("beam_major"), py::arg("beam_minor"),
       py::arg("beam_pa"), py::arg("pixel_scale_x"), py::arg("pixel_scale_y"));
+}
+
+radler::SourceCatalogue::Geometry CatalogueGeometry(size_t width, size_t height,
+                                                    long double pixel_scale_x,
+                                                    long double pixel_scale_y,
+                                                    long double phase_centre_ra,
+                                                    long double phase_centre_dec,
+                                                    long double l_shift, long double m_shift) {
+  radler::SourceCatalogue::Geometry g;
+  g.width = width;
+  g.height = height;
+  g.pixel_scale_x = pixel_scale_x;
+  g.pixel_scale_y = pixel_scale_y;
+  g.phase_centre_ra = phase_centre_ra;
+  g.phase_centre_dec = phase_centre_dec;
+  g.l_shift = l_shift;
+  g.m_shift = m_shift;
+  return g;
+}
+
+template <typename T, typename Get>
+py::array_t<T> CatalogueColumn(const radler::SourceCatalogue& self, Get get) {
+  py::array_t<T> out(py::ssize_t(self.Size()));
+  T* data = out.mutable_data();
+  for (size_t i = 0; i != self.Size(); ++i) data[i] = T(get(self.Sources()[i]));
+  return out;
+}
+
+void InitSourceCatalogue(py::module& m) {
+  using radler::SourceCatalogue;
+  using Source = SourceCatalogue::Source;
+  py::class_<SourceCatalogue>(m, "SourceCatalogue")
+      .def_static("read", &SourceCatalogue::Read, py::arg("path"))
+      .def("__len__", &SourceCatalogue::Size)
+      .def_property_readonly("reference_frequency", &SourceCatalogue::ReferenceFrequency)
+      .def_property_readonly("dropped", &SourceCatalogue::Dropped)
+      .def_property_readonly("names",
+                             [](const SourceCatalogue& self) {
+                               py::list out;
+                               for (const Source& s : self.Sources()) out.append(s.name);
+                               return out;
+                             })
+      .def_property_readonly("types",
+                             [](const SourceCatalogue& self) {
+                               py::list out;
+                               for (const Source& s : self.Sources())
+                                 out.append(s.type == SourceCatalogue::Type::kGaussian
+                                                ? "GAUSSIAN"
+                                                : "POINT");
+                               return out;
+                             })
+      .def_property_readonly("ra",
+                             [](const SourceCatalogue& self) {
+                               return CatalogueColumn<double>(
+                                   self, [](const Source& s) { return s.ra; });
+                             })
+      .def_property_readonly("dec",
+                             [](const SourceCatalogue& self) {
+                               return CatalogueColumn<double>(
+                                   self, [](const Source& s) { return s.dec; });
+                             })
+      .def_property_readonly("flux",
+                             [](const SourceCatalogue& self) {
+                               return CatalogueColumn<float>(
+                                   self, [](const Source& s) { return s.flux; });
+                             })
+      .def_property_readonly("terms",
+                             [](const SourceCatalogue& self) {
+                               py::list out;
+                               for (const Source& s : self.Sources()) {
+                                 py::array_t<float> terms(py::ssize_t(s.terms.size()));
+                                 std::copy(s.terms.begin(), s.terms.end(), terms.mutable_data());
+                                 out.append(terms);
+                               }
+                               return out;
+                             })
+      .def_property_readonly("logarithmic",
+                             [](const SourceCatalogue& self) {
+                               return CatalogueColumn<bool>(
+                                   self, [](const Source& s) { return s.logarithmic; });
+                             })
+      .def_property_readonly("reference_frequencies",
+                             [](const SourceCatalogue& self) {
+                               return CatalogueColumn<double>(
+                                   self, [](const Source& s) { return s.reference_frequency; });
+                             })
+      .def_property_readonly("major",
+                             [](const SourceCatalogue& self) {
+                               return CatalogueColumn<double>(
+                                   self, [](const Source& s) { return s.major; });
+                             })
+      .def_property_readonly("minor",
+                             [](const SourceCatalogue& self) {
+                               return CatalogueColumn<double>(
+                                   self, [](const Source& s) { return s.minor; });
+                             })
+      .def_property_readonly("orientation",
+                             [](const SourceCatalogue& self) {
+                               return CatalogueColumn<double>(
+                                   self, [](const Source& s) { return s.orientation; });
+                             })
+      .def("flux_at",
+           [](const SourceCatalogue& self, const std::vector<double>& frequencies) {
+             // S(nu): (n_freq, n) float32, on the host
+             for (double frequency : frequencies)
+               if (!(frequency > 0.0))
+                 throw std::invalid_argument("flux_at: a frequency is not positive");
+             const std::vector<float> table = self.FluxAt(frequencies);
+             py::array_t<float> out({frequencies.size(), self.Size()});
+             std::copy(table.begin(), table.end(), out.mutable_data());
+             return out;
+           },
+           py::arg("frequencies"))
+      .def("pixel_positions",
+           [](const SourceCatalogue& self, size_t width, size_t height,
+              long double pixel_scale_x, long double pixel_scale_y, long double phase_centre_ra,
+              long double phase_centre_dec, long double l_shift, long double m_shift) {
+             // fractional (x, y) of every source, (n, 2) float64; NaN for a
+             // dropped source (sets `dropped`). Host only.
+             const auto positions = self.PixelPositions(
+                 CatalogueGeometry(width, height, pixel_scale_x, pixel_scale_y, phase_centre_ra,
+                                   phase_centre_dec, l_shift, m_shift));
+             py::array_t<double> out({self.Size(), size_t(2)});
+             for (size_t i = 0; i != self.Size(); ++i) {
+               out.mutable_at(i, 0) = positions[i].first;
+               out.mutable_at(i, 1) = positions[i].second;
+             }
+             return out;
+           },
+           py::arg("width"), py::arg("height"), py::arg("pixel_scale_x"),
+           py::arg("pixel_scale_y"), py::arg("phase_centre_ra"), py::arg("phase_centre_dec"),
+           py::arg("l_shift") = 0.0, py::arg("m_shift") = 0.0)
+      .def("draw_model",
+           [](const SourceCatalogue& self, size_t width, size_t height,
+              long double pixel_scale_x, long double pixel_scale_y, long double phase_centre_ra,
+              long double phase_centre_dec, const std::vector<double>& frequencies,
+              long double l_shift, long double m_shift) {
+             // SourceCatalogue::DrawModel on the default device's session:
+             // (n_freq, height, width). The argument checks come first, so
+             // they are reported where there is no device.
+             const SourceCatalogue::Geometry g =
+                 CatalogueGeometry(width, height, pixel_scale_x, pixel_scale_y, phase_centre_ra,
+                                   phase_centre_dec, l_shift, m_shift);
+             SourceCatalogue::CheckArguments(g, frequencies, nullptr);
+             std::shared_ptr<radler::gpu::Session> session =
+                 radler::gpu::Session::ForDevice(radler::gpu::Session::DefaultDevice());
+             std::vector<aocommon::Image> planes;
+             {
+               py::gil_scoped_release release;
+               planes = self.DrawModel(*session, g, frequencies);
+             }
+             return StackImages(planes, width, height);
+           },
+           py::arg("width"), py::arg("height"), py::arg("pixel_scale_x"),
+           py::arg("pixel_scale_y"), py::arg("phase_centre_ra"), py::arg("phase_centre_dec"),
+           py::arg("frequencies"), py::arg("l_shift") = 0.0, py::arg("m_shift") = 0.0)
+      .def("restore",
+           [](const SourceCatalogue& self, FloatArray images, long double pixel_scale_x,
+              long double pixel_scale_y, long double phase_centre_ra,
+              long double phase_centre_dec, const std::vector<double>& frequencies,
+              long double beam_major, long double beam_minor, long double beam_pa,
+              long double l_shift, long double m_shift) {
+             // SourceCatalogue::Restore on the default device's session: the
+             // images plus the beam-convolved catalogue, as a new array.
+             // (n_freq, h, w), or (h, w) with one frequency.
+             if (images.ndim() != 2 && images.ndim() != 3)
+               throw std::invalid_argument("restore: expected a 2-D image or a 3-D stack");
+             const size_t planes = images.ndim() == 3 ? size_t(images.shape(0)) : 1;
+             if (planes != frequencies.size())
+               throw std::invalid_argument("restore: one plane per frequency expected");
+             const size_t h = images.shape(images.ndim() - 2), w = images.shape(images.ndim() - 1);
+             const SourceCatalogue::Geometry g =
+                 CatalogueGeometry(w, h, pixel_scale_x, pixel_scale_y, phase_centre_ra,
+                                   phase_centre_dec, l_shift, m_shift);
+             SourceCatalogue::Beam beam;
+             beam.major = beam_major;
+             beam.minor = beam_minor;
+             beam.pa = beam_pa;
+             SourceCatalogue::CheckArguments(g, frequencies, &beam);
+             py::array_t<float> out(
+                 std::vector<py::ssize_t>(images.shape(), images.shape() + images.ndim()));
+             std::shared_ptr<radler::gpu::Session> session =
+                 radler::gpu::Session::ForDevice(radler::gpu::Session::DefaultDevice());
+             radler::gpu::Session& s = *session;
+             const float* h_images = images.data();
+             float* h_out = out.mutable_data();
+             const size_t bytes = planes * w * h * sizeof(float);
+             {
+               py::gil_scoped_release release;
+               s.Bind();
+               radler::gpu::Buffer d_images(s, bytes);
+               s.H2D(d_images.Ptr(), h_images, bytes);
+               self.Restore(s, d_images.F(), g, frequencies, beam);
+               s.D2H(h_out, d_images.Ptr(), bytes);
+             }
+             return out;
+           },
+           py::arg("images"), py::arg("pixel_scale_x"), py::arg("pixel_scale_y"),
+           py::arg("phase_centre_ra"), py::arg("phase_centre_dec"), py::arg("frequencies"),
+           py::arg("beam_major"), py::arg("beam_minor"), py::arg("beam_pa"),
+           py::arg("l_shift") = 0.0, py::arg("m_shift") = 0.0);
 }
 
 py::dict ResultDict(const radler::algorithms::ParallelDeconvolutionResult& r,
@@ -1267,6 +1469,7 @@ PYBIND11_MODULE(radler, m) {  // python/pywrappers.cc
   InitRadler(m);
   InitComponentList(m);
   InitRestore(m);
+  InitSourceCatalogue(m);
   InitGpu(m);
   InitTiling(m);
   InitDistributed(m);
