@@ -1,4 +1,4 @@
-// The float64 row plans (the padded residual corrections): 74 plans, two
+// The float64 row plans (the padded residual corrections): 71 plans, two
 // kernels each, in a unit of their own so that no FFT unit bounds the build.
 // The kernels are fft_fast_rows.h's; the float plans and the launchers are
 // in fft_fast_rows.hip.
