@@ -17,16 +17,9 @@
 #include "device.h"
 #include "psf_offset.h"
 #include "settings.h"
+#include "subimage_split.h"
 
 namespace radler::algorithms {
-
-/// One tile of the grid (parallel_deconvolution.h SubImage).
-struct SubImage {
-  size_t index = 0, x = 0, y = 0, width = 0, height = 0;
-  std::vector<bool> mask, boundary_mask;
-  double peak = 0.0;
-  bool reached_major_threshold = false;
-};
 
 struct ParallelDeconvolutionResult {
   bool another_iteration_required = false;
@@ -112,38 +105,31 @@ class ParallelDeconvolution {
       const std::vector<gpu::Planes>& psf_images,
       const std::vector<PsfOffset>& psf_offsets, double major_loop_gain);
 
-  void RunSubImage(SubImage& sub, ImageSet& data_image, const ImageSet& model_image,
-                   ImageSet& result_model, const gpu::Planes& psfs,
-                   double major_iteration_threshold, bool find_peak_only);
-  /// Runs the subimage's algorithm; returns whether it converged.
-  bool DeconvolveSubImage(SubImage& sub, ImageSet& sub_data, ImageSet& sub_model,
-                          const gpu::Planes& sub_psfs,
-                          double major_iteration_threshold, bool find_peak_only);
-  /// Per-subimage result of a concurrent pass (device planes on the main
+  struct Pass;         // what one pass over the subimages works on
+  struct SubImageRun;  // one subimage's device planes through a pass
+  /// Per-subimage result of a snapshot pass (device planes on the main
   /// device, valid during the call): the residual box, the model box to add
   /// (the initial one when it diverged) and whether it converged.
   using SubImageSink = std::function<void(size_t index, const float* d_data,
                                           const float* d_model, bool converging)>;
-  /// Runs the subimages (those with run[i] != 0 when `run` is given) on the
-  /// worker pool; merges the results in subimage order, or hands each to
-  /// `sink` in subimage order instead.
-  void RunSubImagesConcurrently(ImageSet& data_image, const ImageSet& model_image,
-                                ImageSet& result_model,
-                                const std::vector<gpu::Planes>& psf_images,
-                                const std::vector<size_t>& psf_indices,
-                                double major_iteration_threshold,
-                                bool find_peak_only,
-                                const std::vector<char>* run = nullptr,
+
+  /// Sequential, pool or distributed; returns the start peak.
+  double RunPass(const Pass& pass);
+  /// Runs the algorithm of `sub`; returns whether it converged.
+  bool DeconvolveSubImage(SubImage& sub, ImageSet& sub_data, ImageSet& sub_model,
+                          const gpu::Planes& sub_psfs, double major_iteration_threshold,
+                          bool find_peak_only);
+  /// The subimages (those with run[i] != 0, given `run`) one after another on
+  /// the calling thread. Without a sink each is merged at once and the next sees
+  /// it (the reference with one thread); with one, all see the pass-start residual.
+  void RunSubImagesInTurn(const Pass& pass, const std::vector<char>* run = nullptr,
+                          const SubImageSink& sink = nullptr);
+  /// The same on the worker pool, every one from the pass-start residual; the
+  /// results are merged, or handed to `sink`, in subimage order.
+  void RunSubImagesConcurrently(const Pass& pass, const std::vector<char>* run = nullptr,
                                 const SubImageSink& sink = nullptr);
-  /// Process-per-GPU split: this rank deconvolves the subimages it owns
-  /// (SubImageOwner) from the pass-start residual, then every subimage's
-  /// boxes are broadcast by their owner and merged by all ranks in subimage
-  /// order. Returns the global start peak for the find-peak pass.
-  double RunSubImagesDistributed(ImageSet& data_image, const ImageSet& model_image,
-                                 ImageSet& result_model,
-                                 const std::vector<gpu::Planes>& psf_images,
-                                 const std::vector<size_t>& psf_indices,
-                                 double major_iteration_threshold, bool find_peak_only);
+  /// Process-per-GPU split; returns the global start peak (find-peak pass).
+  double RunSubImagesDistributed(const Pass& pass);
   void EnsureWorkers(gpu::Session& main, size_t n);
   /// the subimage's box of the full-image scale masks into its algorithm
   void LoadScaleMasks(const SubImage& sub, size_t width);
@@ -175,15 +161,22 @@ class ParallelDeconvolution {
   std::mutex masks_mutex_;
 };
 
-/// Subimage geometry of the grid (parallel_deconvolution.cc:57-166).
-std::vector<SubImage> MakeSubImages(const std::vector<float>& image, size_t width,
-                                    size_t height, const bool* user_mask,
-                                    const std::vector<PsfOffset>& psf_offsets,
-                                    const Settings& settings,
-                                    std::vector<size_t>& psf_indices);
+/// A subimage's work in a pass, for the pool's queue and the ranks' LptOwners:
+/// cleaning grows with the area and with how far the peak lies above the threshold
+/// (components ~ log(peak / threshold) per source at a fixed gain); finding, with area.
+double SubImageCost(size_t area, double peak, double threshold, bool find_peak_only);
 
-/// parallel_deconvolution.cc:34-55 (first index on equal distance).
-size_t NearestPsfIndex(const std::vector<PsfOffset>& psf_offsets, size_t x,
-                       size_t y) noexcept;
+/// How the pool's workers share the subimages of a pass.
+struct PoolAssignment {
+  std::vector<size_t> order;    // the subimages in the order they are taken
+  bool shared_counter = false;  // a free worker takes order[next++]; else w: w, w + W, ...
+  std::vector<char> staged;     // per subimage: trimmed on the main device, peer-copied
+};
+
+/// For `queue_mode` (RADLER_POOL_QUEUE, see the definition) and the subimages with
+/// run[i] != 0 (all without `run`), costs[i] each; worker_local[w]: on the main device.
+PoolAssignment AssignPool(int queue_mode, const std::vector<char>& worker_local,
+                          bool force_staging, const std::vector<double>& costs,
+                          const std::vector<char>* run = nullptr);
 
 }  // namespace radler::algorithms

@@ -45,6 +45,8 @@ class Radler {
       const;
   bool IsInitialized() const;
   size_t IterationNumber() const;
+  /// Perform has left the auto-mask tracking phase: the masks are now used.
+  bool AutoMaskIsFinished() const { return auto_mask_is_finished_; }
 
   // MI355X build only: the device session (bench / tests) and the
   // parallel-deconvolution object.

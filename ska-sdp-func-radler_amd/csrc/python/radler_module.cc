@@ -445,6 +445,7 @@ void InitRadler(py::module& m) {  // python/pyradler.cc
            py::arg("major_iteration_number"))
       .def("set_communicator", &radler::Radler::SetCommunicator, py::arg("communicator"))
       .def_property_readonly("iteration_number", &radler::Radler::IterationNumber)
+      .def_property_readonly("auto_mask_is_finished", &radler::Radler::AutoMaskIsFinished)
       .def_property_readonly("component_list", &radler::Radler::GetComponentList)
       // what ComponentList::WriteSources takes from MaxScaleCountAlgorithm():
       // its fitter (a copy) and the scale sizes ([0] unless multiscale)
@@ -882,6 +883,25 @@ void InitTiling(py::module& m) {
     }
     return py::make_tuple(boxes, labels);
   }, py::arg("image"), py::arg("grid_width"), py::arg("grid_height"));
+  t.def("pool_assignment", [](int queue_mode, const std::vector<bool>& worker_local,
+                              bool force_staging, const std::vector<double>& costs,
+                              const std::optional<std::vector<bool>>& run) {
+    if (worker_local.empty()) throw std::invalid_argument("pool_assignment: no workers");
+    const std::vector<char> local(worker_local.begin(), worker_local.end());
+    std::vector<char> selected;
+    if (run) {
+      if (run->size() != costs.size()) throw std::runtime_error("run and costs differ in length");
+      selected.assign(run->begin(), run->end());
+    }
+    const auto plan = radler::algorithms::AssignPool(queue_mode, local, force_staging, costs,
+                                                     run ? &selected : nullptr);
+    return py::make_tuple(plan.order, plan.shared_counter,
+                          std::vector<bool>(plan.staged.begin(), plan.staged.end()));
+  }, py::arg("queue_mode"), py::arg("worker_local"), py::arg("force_staging"), py::arg("costs"),
+     py::arg("run") = py::none(),
+     "The worker pool's share-out of a pass (AssignPool): (order the subimages are taken in, "
+     "whether workers claim from one shared counter (else worker w of W takes order[w], "
+     "order[w + W], ...), per subimage whether it is staged on the main device)");
 
   // math::DijkstraSplitter (cpp/math/dijkstra_splitter.h) member by member,
   // for the restated cpp/math/test/test_dijkstra_splitter.cc. Images are

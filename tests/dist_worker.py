@@ -35,8 +35,10 @@ def host_communicator(rd, rank, world):
     return rd.distributed.HostCommunicator(world, rank, broadcast, allreduce_max)
 
 
-def tiled_settings(rd, kind, w, thr, max_iter, mgain, gw, gh):
+def tiled_settings(rd, kind, w, thr, max_iter, mgain, gw, gh, threads=None):
     s = rd.Settings()
+    if threads is not None:  # else the processor count: every rank runs a pool
+        s.parallel.max_threads = threads
     s.algorithm_type = (rd.AlgorithmType.multiscale if kind == 1
                         else rd.AlgorithmType.generic_clean)
     s.trimmed_image_width = s.trimmed_image_height = w
@@ -76,6 +78,8 @@ def main():
     ap.add_argument("--majors", type=int, default=2)
     ap.add_argument("--channels", type=int, default=1,
                     help="joined channels (tests/config_problems.joined_channels)")
+    ap.add_argument("--threads", type=int, default=None,
+                    help="settings.parallel.max_threads (1: a rank without a worker pool)")
     args = ap.parse_args()
 
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -114,13 +118,43 @@ def main():
             out[f"trace{major}"] = run.trace(0)
         run.sync()
         del run
+    elif args.case == "automask":
+        # Radler.perform's auto-mask state machine over a gridded multiscale
+        # run (tests/test_automask.py's tiled problem): the owners' tracked
+        # scale masks reach the other ranks by the second broadcast
+        from synthetic import problem
+        w = args.size
+        gw, gh = args.grid
+        psf, dirty = problem(w, w, 40, 4, seed=91, noise=1e-3)
+        s = tiled_settings(rd, 1, w, 0.0, 3000, 0.8, gw, gh, args.threads)
+        s.minor_loop_gain = 0.1
+        s.auto_mask_sigma = 6.0
+        s.auto_threshold_sigma = 1.5  # the deeper threshold of the phase that uses the masks
+        s.major_iteration_count = 20
+        residual, model = dirty.copy(), np.zeros_like(dirty)
+        r = rd.Radler(s, psf, residual, model, 2.0 * PIXEL_SCALE)
+        r.set_communicator(comm)
+        # at most --majors major iterations, until no further one is asked for
+        out["phase_left_after"] = np.int64(0)  # the major iteration that left the tracking phase
+        for major in range(args.majors):
+            another = r.perform(major + 1)
+            out[f"another{major}"] = np.int64(another)
+            out[f"residual{major}"] = residual.copy()
+            out[f"model{major}"] = model.copy()
+            out[f"iterations{major}"] = np.int64(rd.gpu.total_iteration_number(r))
+            if r.auto_mask_is_finished and out["phase_left_after"] == 0:
+                out["phase_left_after"] = np.int64(major + 1)
+            out["majors"] = np.int64(major + 1)
+            if not another:
+                break
+        del r
     else:
         w = args.size
         gw, gh = args.grid
         psf, dirty = tiled_problem(w, gw, args.channels)
         thr, max_iter = 4e-3, 1500
         mgain = 0.9 if args.majors == 1 else 0.5
-        s = tiled_settings(rd, args.kind, w, thr, max_iter, mgain, gw, gh)
+        s = tiled_settings(rd, args.kind, w, thr, max_iter, mgain, gw, gh, args.threads)
         run = rd.gpu.DeviceRun(s, psf, dirty, [1.0] * args.channels if args.channels > 1 else [],
                                2.0 * PIXEL_SCALE if args.kind == 1 else 0.0)
         run.set_communicator(comm)

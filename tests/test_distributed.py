@@ -13,7 +13,8 @@ GPU (gloo, world 2 and 3, all ranks on cuda:0): distributed tiled runs vs the
 oracle (same tiles, per-subimage traces identical, residual/model within
 2e-5 * max|dirty|) and vs each other (bit-identical on every rank), for one
 field and for joined channels (4 and 8 channels, the C3 image set split by
-subimage).
+subimage); ranks without a worker pool (max_threads 1) bit-identical to the
+pooled ones; auto-mask tracking over two ranks bit-identical to one.
 """
 import os
 import socket
@@ -101,12 +102,48 @@ def test_host_communicator_gloo_world2(tmp_path):
     # joined channels split by subimage over the ranks
     (2, 1, 256, 2, 2, 4), (3, 1, 256, 3, 2, 8),
     (1, 1, 256, 3, 2, 8), (2, 1, 256, 3, 2, 8), (3, 1, 256, 3, 2, 4), (3, 1, 256, 3, 2, 1)])
-def test_distributed_tiled_matches_oracle_snapshot(tmp_path, world, kind, w, gw, gh, channels):
+def test_distributed_tiled_matches_oracle_snapshot(tiled_outs, world, kind, w, gw, gh, channels):
+    _check_tiled_against_oracle(tiled_outs, world, kind, w, gw, gh, channels)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,w", [(1, 256), (0, 192)])
+def test_distributed_tiled_rank_without_pool(tiled_outs, kind, w):
+    """settings.parallel.max_threads = 1: every rank runs its subimages one
+    after another on its main session, each from the pass-start residual.
+    Same oracle-snapshot assertions as the pooled cases, and every output
+    bit-identical to the same case with the pool."""
+    outs = _check_tiled_against_oracle(tiled_outs, 2, kind, w, 2, 2, 1, threads=1)
+    pooled = tiled_outs(2, kind, w, 2, 2, 1, 2, None)
+    for o, p in zip(outs, pooled):
+        assert sorted(o) == sorted(p)
+        for key in o:
+            assert np.array_equal(o[key], p[key]), key
+
+
+@pytest.fixture(scope="module")
+def tiled_outs(tmp_path_factory):
+    """get(world, kind, w, gw, gh, channels, majors, threads): the ranks' outputs
+    of a tiled case, launched once in this module whichever test asks first,
+    and not modified."""
+    outs = {}
+
+    def get(*case):
+        if case not in outs:
+            world, kind, w, gw, gh, channels, majors, threads = case
+            extra = [] if threads is None else ["--threads", str(threads)]
+            outs[case] = _launch(
+                tmp_path_factory.mktemp("tiled"), world, "tiled",
+                ["--kind", str(kind), "--size", str(w), "--grid", str(gw), str(gh),
+                 "--majors", str(majors), "--channels", str(channels), *extra])
+        return outs[case]
+    return get
+
+
+def _check_tiled_against_oracle(tiled_outs, world, kind, w, gw, gh, channels, threads=None):
     from dist_worker import tiled_problem
     majors = 2
-    outs = _launch(tmp_path, world, "tiled",
-                   ["--kind", str(kind), "--size", str(w), "--grid", str(gw), str(gh),
-                    "--majors", str(majors), "--channels", str(channels)])
+    outs = tiled_outs(world, kind, w, gw, gh, channels, majors, threads)
     h = w
     psf, dirty = tiled_problem(w, gw, channels)
     if channels == 1:
@@ -146,6 +183,42 @@ def test_distributed_tiled_matches_oracle_snapshot(tmp_path, world, kind, w, gw,
         dm = np.abs(outs[0][f"model{major}"].reshape(mod_o.shape) - mod_o).max()
         print(f"major {major}: residual {dr:.3g}, model {dm:.3g} (tolerance {tol:.3g})")
         assert dr <= tol and dm <= tol, (dr, dm, tol)
+    return outs
+
+
+AUTOMASK_ARGS = ["--size", "256", "--grid", "2", "2", "--majors", "8"]
+
+
+@pytest.fixture(scope="module")
+def automask_one_process(tmp_path_factory):
+    return _launch(tmp_path_factory.mktemp("automask_one"), 1, "automask", AUTOMASK_ARGS)[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("threads", [None, 1])
+def test_distributed_automask_equals_one_process(tmp_path, automask_one_process, threads):
+    """Auto-mask tracking over ranks (the only user of the scale-mask second
+    broadcast): a multiscale 2 x 2 run of Radler.perform with auto-masking,
+    until it asks for no further major iteration. Two major iterations do
+    not leave the tracking phase on this problem, and masks are only written
+    while tracking, so the run goes on until the phase was left and at least
+    one further major iteration cleaned inside the masks: with wrong masks on
+    a rank that did not track them its components would differ. World 2,
+    with worker pools and without (threads 1), ends every major iteration
+    with residual, model and iteration count bit-identical to world 1, on
+    both ranks."""
+    one = automask_one_process
+    left, majors = int(one["phase_left_after"]), int(one["majors"])
+    print(f"tracking phase left after major {left} of {majors}; components per major:",
+          [int(one[f"iterations{m}"]) for m in range(majors)])
+    assert 1 <= left < majors, (left, majors)
+    # the masks were used: components were cleaned after the phase was left
+    assert one[f"iterations{majors - 1}"] > one[f"iterations{left - 1}"]
+    extra = [] if threads is None else ["--threads", str(threads)]
+    for o in _launch(tmp_path, 2, "automask", AUTOMASK_ARGS + extra):
+        assert sorted(o) == sorted(one)
+        for key in one:
+            assert np.array_equal(o[key], one[key]), key
 
 
 @pytest.mark.gpu

@@ -3,7 +3,8 @@
 CPU: the product's host splitter (radler.tiling.make_subimages ->
 libradler_amd.so MakeSubImages / DijkstraSplitter) produces exactly the
 oracle's subimage geometry (boxes and boundary masks), the masks partition the
-image, boxes are even-sized on even images.
+image, boxes are even-sized on even images; the worker pool's share-out of a
+pass (radler.tiling.pool_assignment -> AssignPool) per queue mode.
 GPU: Radler's tiled major iteration (device box transfers + per-subimage
 algorithms) matches the oracle's tiled run: same tiles, same per-subimage
 component traces, residual/model within 2e-5 * max|dirty|.
@@ -91,6 +92,49 @@ def test_splitter_key_order_search_matches_oracle(kind):
         assert used[1] > 0
     if kind == "fine_quantized":  # key-order paths completed from an exact prefix
         assert used[2] > 0
+
+
+POOL_COSTS = [3.0, 8.0, 5.0, 2.0, 8.0]
+INDEX_ORDER, COST_ORDER = [0, 1, 2, 3, 4], [1, 4, 2, 0, 3]  # stable on the tie of 8
+
+
+@pytest.mark.parametrize("mode,order,shared", [
+    (0, INDEX_ORDER, False), (1, COST_ORDER, True), (2, INDEX_ORDER, True),
+    (3, COST_ORDER, False), (-1, INDEX_ORDER, False), (4, INDEX_ORDER, False)])
+def test_pool_assignment_modes(mode, order, shared):
+    """The pool's share-out of a pass as the driver computes it (AssignPool),
+    two workers on the main device: strided, worker 0 takes order[0], [2],
+    [4]; unknown modes are mode 0. Nothing is staged."""
+    got = rd.tiling.pool_assignment(mode, [True, True], False, POOL_COSTS)
+    assert got == (order, shared, [False] * 5)
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2, 3])
+def test_pool_assignment_falls_back_to_fixed(mode):
+    """A worker on another device, or forced staging: every mode is the fixed
+    round robin in index order; the staged subimages are the remote worker's
+    (every second one), or all."""
+    assert rd.tiling.pool_assignment(mode, [True, False], False, POOL_COSTS) == \
+        (INDEX_ORDER, False, [False, True, False, True, False])
+    assert rd.tiling.pool_assignment(mode, [False, True], False, POOL_COSTS) == \
+        (INDEX_ORDER, False, [True, False, True, False, True])
+    assert rd.tiling.pool_assignment(mode, [True, True], True, POOL_COSTS) == \
+        (INDEX_ORDER, False, [True] * 5)
+
+
+def test_pool_assignment_subset():
+    """`run` restricts the pass (a rank's own subimages): only those appear,
+    and the round robin counts positions among them."""
+    run = [True, False, True, True, True]
+    assert rd.tiling.pool_assignment(1, [True, True], False, POOL_COSTS, run) == \
+        ([4, 2, 0, 3], True, [False] * 5)
+    assert rd.tiling.pool_assignment(0, [True, True], False, POOL_COSTS, run) == \
+        ([0, 2, 3, 4], False, [False] * 5)
+    # subimages 2 and 4 are the 2nd and 4th of the subset: the remote worker's
+    assert rd.tiling.pool_assignment(1, [True, False], False, POOL_COSTS, run) == \
+        ([0, 2, 3, 4], False, [False, False, True, False, True])
+    with pytest.raises(ValueError):
+        rd.tiling.pool_assignment(1, [], False, POOL_COSTS)
 
 
 def _settings(kind, w, thr, max_iter, mgain, gw, gh, threads):
