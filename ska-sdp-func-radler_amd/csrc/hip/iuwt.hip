@@ -9,6 +9,7 @@
 // Decompose(x, x, ..) — input used as its own scratch, as the reference's IUWT
 // deconvolution does — makes the first horizontal pass a recursive in-place row
 // filter; that case runs one thread per row, left to right.
+#include "iuwt_chain_plan.h"
 #include "rdl_internal.h"
 
 namespace rdl {
@@ -359,20 +360,7 @@ __device__ __forceinline__ float VerticalByRegion(const float* t, int region) {
 // above (HorizontalValue / VerticalValue and the subtraction), so the planes
 // are bit-identical; a segment of K outputs reads K + 8 rows of a (the tap
 // rows of its first and last outputs), the strip 4d extra columns each side.
-struct ChainArgs {
-  const float* a;     // this scale's approximation (decompose) / the coarser
-                      // recomposition (recompose)
-  float* i1;          // next approximation (decompose) / finer recomposition
-  float* coef;        // this scale's coefficients: written (decompose) or
-                      // added (recompose)
-  uint32_t w, h;
-  int d;
-  uint32_t ws;        // output columns per workgroup (multiple of 4, <= 1024)
-  uint32_t n_strips;  // ceil(w / ws)
-  uint32_t n_seg;     // segments per chain
-  uint32_t n_res;     // chains: min(d, h) residues
-  float* dummy;       // 256 floats: the stores of lanes with nothing to store
-};
+// (ChainArgs, the arguments of one launch: iuwt_chain_plan.h)
 // block -> (residue r, segment, strip), consecutive strips of one segment on
 // one XCD (their halo columns are shared through its L2)
 struct ChainPlace {
@@ -705,54 +693,6 @@ inline int IuwtMode() {
 }
 inline bool IuwtFusedOn() { return IuwtMode() != 0; }
 
-// the chain launch's geometry for spacing d, or false when the rows do not
-// fit its register/LDS budget (the row kernels then run)
-struct ChainPlan {
-  ChainArgs a;
-  unsigned blocks;
-  size_t lds;
-  int na, no, ni;  // float4 loads per thread per row; output and halo-strip
-                   // columns per thread (multiples of 256)
-};
-inline bool PlanChain(uint32_t w, uint32_t h, int d, bool decompose, ChainPlan* pl) {
-  // 512 columns per workgroup at every spacing: 1024 (fewer halo columns at
-  // d >= 31) lowers the occupancy more than it saves (r06 measurement)
-  uint32_t ws = 512u;
-  if (const char* e = std::getenv("RDL_IUWT_CHAIN_WS")) {  // (measurement)
-    const unsigned v = unsigned(std::atoi(e));
-    if (v >= 256 && v <= 1024 && v % 256 == 0) ws = v;
-  }
-  if (ws > (w + 3u) / 4u * 4u) ws = (w + 3u) / 4u * 4u;
-  const int64_t halo = decompose ? 4 * int64_t(d) : 2 * int64_t(d);
-  const int64_t wa4 = (int64_t(ws) + 2 * halo + 6) / 4;
-  if (wa4 > 512) return false;
-  pl->na = wa4 <= 256 ? 1 : 2;
-  pl->no = int(DivUp(ws, 256));
-  if (pl->no == 3) pl->no = 4;
-  const int64_t wi = int64_t(ws) + 4 * int64_t(d);
-  pl->ni = std::max(pl->no, int((wi + 255) / 256));
-  if (pl->ni > pl->no + 2) return false;
-  const uint32_t n_strips = (w + ws - 1) / ws;
-  const uint32_t n_res = uint32_t(d) < h ? uint32_t(d) : h;  // chains with rows
-  const uint32_t k_max = (h + uint32_t(d) - 1) / uint32_t(d);
-  uint32_t n_seg = std::min(DivUp(k_max, 24), DivUp(1536, size_t(n_res) * n_strips));
-  n_seg = std::max(1u, std::min(n_seg, k_max));
-  const uint64_t n_blocks = uint64_t(n_res) * n_seg * n_strips;
-  if (n_blocks > (uint64_t(1) << 30)) return false;
-  ChainArgs& a = pl->a;
-  a.w = w;
-  a.h = h;
-  a.d = d;
-  a.ws = ws;
-  a.n_strips = n_strips;
-  a.n_seg = n_seg;
-  a.n_res = n_res;
-  pl->blocks = unsigned(8 * ((n_blocks + 7) / 8));
-  const int64_t slots = 2 * 1024 * int64_t(pl->na);
-  pl->lds = decompose ? size_t(slots + 7 * wi + 11 * int64_t(ws)) * sizeof(float)
-                      : size_t(slots + 5 * int64_t(ws)) * sizeof(float);
-  return pl->lds <= 160 * 1024;
-}
 template <typename Fn>
 int LaunchChainKernel(rdl_session* s, const ChainPlan& pl, Fn* fn,
                       std::atomic<uint64_t>& lds_set) {
@@ -839,9 +779,10 @@ int rdl_iuwt_decompose(rdl_session* s, float* d_input, float* d_scratch,
     // planes alternate between the largest-scale plane and one scratch plane,
     // the last landing in the largest-scale plane.
     std::vector<rdl::ChainPlan> plans(n_scales);
+    const char* ws_override = std::getenv("RDL_IUWT_CHAIN_WS");
     bool all = true;
     for (uint32_t sc = 0; sc < n_scales && all; ++sc)
-      all = rdl::PlanChain(width, height, (1 << (sc + 1)) - 1, true, &plans[sc]);
+      all = rdl::PlanChain(width, height, (1 << (sc + 1)) - 1, true, ws_override, &plans[sc]);
     if (all) {
       RDL_TRY(s->EnsureScratch(s->iuwt, (n + 256) * sizeof(float)));
       float* big = d_coeffs + size_t(n_scales) * n;
@@ -942,9 +883,11 @@ int rdl_iuwt_recompose(rdl_session* s, const float* d_coeffs, uint32_t width,
     // between the scratch plane and d_out so that the last lands in d_out
     const int first = include_largest ? int(n_scales) : int(n_scales) - 1;
     std::vector<rdl::ChainPlan> plans(static_cast<size_t>(first));
+    const char* ws_override = std::getenv("RDL_IUWT_CHAIN_WS");
     bool all = true;
     for (int sc = 0; sc < first && all; ++sc)
-      all = rdl::PlanChain(width, height, (1 << (sc + 1)) - 1, false, &plans[size_t(sc)]);
+      all = rdl::PlanChain(width, height, (1 << (sc + 1)) - 1, false, ws_override,
+                           &plans[size_t(sc)]);
     if (all) {
       for (auto& pl : plans) pl.a.dummy = tmp + n;
       const float* prev = d_coeffs + size_t(first) * n;

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "div_up.h"
 #include "rdl_hip.h"
 
 namespace rdl {
@@ -435,8 +436,6 @@ __device__ __forceinline__ void PeakArrive(const PeakFinish& f, uint64_t* lds) {
     __hip_atomic_store(f.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-
-inline unsigned DivUp(size_t a, size_t b) { return unsigned((a + b - 1) / b); }
 
 }  // namespace rdl
 
