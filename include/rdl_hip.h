@@ -56,6 +56,13 @@ int rdl_session_destroy(rdl_session* s);
  * cpp/radler.cc); this is the device-side counterpart of process teardown. */
 int rdl_shutdown(void);
 int rdl_session_sync(rdl_session* s);
+/* Makes the session's device current for the calling thread and waits for
+ * every stream of that device, this library's or not (hipDeviceSynchronize).
+ * For the one place where code that is not this library's has been given
+ * device memory and a stream of its own choosing: a user-written Python
+ * deconvolution function. RDL_ERR_ARG for a NULL session and
+ * after rdl_shutdown. */
+int rdl_device_sync(rdl_session* s);
 /* hipStream_t of the session, for callers that record events on it. */
 void* rdl_session_stream(rdl_session* s);
 /* Two launch lanes on one session, for independent chains that overlap on

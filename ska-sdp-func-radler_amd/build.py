@@ -77,6 +77,22 @@ def link(cmd_prefix, out, rest):
     os.replace(tmp, out)
 
 
+def aten_dlpack_flags():
+    """PyTorch's copy of dlpack.h for csrc/python/dlpack_abi.h, when torch is
+    installed (located without importing it); the header restates the structs
+    otherwise. After every other include directory: torch ships headers of
+    other projects too."""
+    import importlib.util
+    try:
+        spec = importlib.util.find_spec("torch")
+    except (ImportError, ValueError):
+        spec = None
+    for base in (spec.submodule_search_locations or []) if spec else []:
+        if os.path.exists(os.path.join(base, "include", "ATen", "dlpack.h")):
+            return ["-DRADLER_HAVE_ATEN_DLPACK", "-idirafter", os.path.join(base, "include")]
+    return []
+
+
 def build(jobs=8, verbose=False):
     os.makedirs(BUILD, exist_ok=True)
     os.makedirs(LIB, exist_ok=True)
@@ -117,7 +133,8 @@ def build(jobs=8, verbose=False):
         ext = sysconfig.get_config_var("EXT_SUFFIX")
         mod = os.path.join(PKG, "radler" + ext)
         py_flags = [*CXX_FLAGS, f"-I{pybind11.get_include()}",
-                    f"-I{sysconfig.get_paths()['include']}", "-fvisibility=hidden"]
+                    f"-I{sysconfig.get_paths()['include']}", "-fvisibility=hidden",
+                    *aten_dlpack_flags()]
         py_objs, items = [], []
         for src in py_srcs:
             obj = os.path.join(BUILD, "py_" + os.path.basename(src) + ".o")

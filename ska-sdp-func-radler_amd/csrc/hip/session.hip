@@ -612,6 +612,14 @@ int rdl_session_sync(rdl_session* s) {
   return RDL_OK;
 }
 
+int rdl_device_sync(rdl_session* s) {
+  RDL_ARG_CHECK(s, "session is NULL");
+  RDL_ARG_CHECK(!rdl::ShutDown(), "rdl_shutdown has run");
+  RDL_HIP_CHECK(hipSetDevice(s->device));
+  RDL_HIP_CHECK(hipDeviceSynchronize());
+  return RDL_OK;
+}
+
 void* rdl_session_stream(rdl_session* s) { return s ? s->stream : nullptr; }
 
 int rdl_session_bind(rdl_session* s) {

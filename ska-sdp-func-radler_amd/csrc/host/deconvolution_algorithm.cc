@@ -1,11 +1,31 @@
 #include "deconvolution_algorithm.h"
 
+#include <atomic>
 #include <stdexcept>
 #include <string>
 
 #include "logpoly.h"
+#include "python_deconvolution_factory.h"
 
 namespace radler::algorithms {
+
+namespace {
+std::atomic<PythonDeconvolutionFactory> python_factory{nullptr};
+}
+
+void SetPythonDeconvolutionFactory(PythonDeconvolutionFactory factory) {
+  python_factory.store(factory);
+}
+
+std::unique_ptr<DeconvolutionAlgorithm> MakePythonDeconvolution(
+    const std::string& filename) {
+  const PythonDeconvolutionFactory factory = python_factory.load();
+  if (!factory)
+    throw std::runtime_error(
+        "Python deconvolution needs the radler Python module loaded in the process: "
+        "the module hosts the algorithm, and this library embeds no interpreter");
+  return factory(filename);
+}
 
 void DeconvolutionAlgorithm::SetSpectrallyForcedImages(
     std::vector<std::vector<float>> planes, size_t width) {

@@ -120,6 +120,11 @@ class DeconvolutionAlgorithm {
     return *spectral_fitter_;
   }
   bool HasSpectralFitter() const { return spectral_fitter_ != nullptr; }
+  /// The fitter as the clones share it, for a holder that may outlive this
+  /// algorithm (the `meta` of a Python deconvolution function).
+  const std::shared_ptr<const schaapcommon::fitters::SpectralFitter>& SharedFitter() const {
+    return spectral_fitter_;
+  }
 
   // deconvolution_algorithm.h:163-166: width x height factors every peak
   // search multiplies in (local-RMS thresholding); nullptr clears it

@@ -342,6 +342,10 @@ rdl_subminor* Session::SharedSubminor() {
 void Session::Sync() {
   prof::Section p("gpu.sync");
   Check(rdl_session_sync(s_), "rdl_session_sync"); }
+void Session::DeviceSync() {
+  prof::Section p("gpu.device_sync");
+  Check(rdl_device_sync(s_), "rdl_device_sync");
+}
 void Session::Bind() { Check(rdl_session_bind(s_), "rdl_session_bind"); }
 void Session::SetConcurrency(size_t n) {
   Check(rdl_session_set_concurrency(s_, uint32_t(n)), "rdl_session_set_concurrency");

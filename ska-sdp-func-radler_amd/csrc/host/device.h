@@ -166,6 +166,9 @@ class Session {
   bool IsWorker() const { return worker_; }
   Fft& GetFft(size_t width, size_t height, bool f64 = false);
   void Sync();
+  /// Bind(), then wait for every stream of the device, foreign ones included
+  /// (rdl_device_sync): after user code ran on a stream of its own.
+  void DeviceSync();
   /// Make this session's device current for the calling thread.
   void Bind();
   /// `n` sessions share the device concurrently (caps cooperative grids).

@@ -17,6 +17,7 @@
 #include "iuwt_deconvolution.h"
 #include "multiscale_algorithm.h"
 #include "parallel_deconvolution.h"
+#include "python_deconvolution_factory.h"
 #include "rms_image.h"
 
 namespace radler {
@@ -321,8 +322,9 @@ void Radler::InitializeDeconvolutionAlgorithm(
       break;
     case AlgorithmType::kMoreSane:
       Unsupported("MoreSane");
-    case AlgorithmType::kPython:
-      Unsupported("Python deconvolution");
+    case AlgorithmType::kPython:  // :371-374; hosted by the Python module
+      algorithm = algorithms::MakePythonDeconvolution(settings_.python.filename);
+      break;
   }
   algorithm->SetMaxIterations(settings_.minor_iteration_count);
   algorithm->SetThreshold(settings_.absolute_threshold);

@@ -26,6 +26,7 @@
 #include "fft_sizes.h"
 #include "host_profile.h"
 #include "multiscale_transforms.h"
+#include "python_deconvolution.h"
 #include "subminor.h"
 
 namespace py = pybind11;
@@ -126,7 +127,28 @@ void InitSettings(py::module& m) {  // python/pysettings.cc
       .def_readwrite("location", &radler::Settings::MoreSane::location)
       .def_readwrite("arguments", &radler::Settings::MoreSane::arguments)
       .def_readwrite("sigma_levels", &radler::Settings::MoreSane::sigma_levels);
-  py::class_<radler::Settings::Python>(settings, "Python")
+  py::class_<radler::Settings::Python>(
+      settings, "Python",
+      "algorithm_type = AlgorithmType.python: `filename` is a Python file, evaluated once "
+      "when the Radler object is made, in a namespace of its own. It defines\n"
+      "  deconvolve(residual, model, psf, meta): new C-contiguous float64 numpy arrays, "
+      "residual and model of shape (n_freq, n_pol, height, width), psf (n_freq, height, "
+      "width); returns {'residual': array, 'model': array, 'level': peak, 'continue': "
+      "bool}; or\n"
+      "  deconvolve_device(residual, model, psf, meta): radler.gpu.DeviceArray views "
+      "(float32, the same shapes) of the image sets' own device memory, for "
+      "torch.from_dlpack; residual and model are edited in place, psf is read-only; "
+      "returns {'level': peak, 'continue': bool}, optionally with 'residual' / 'model' "
+      "as another float32, C-contiguous device array of the same shape, which is then "
+      "copied. deconvolve_device wins when both are defined.\n"
+      "Element [f, p] is image f * n_pol + p. meta has channels (.frequency, .weight), "
+      "iteration_number (writable), final_threshold, gain, max_iterations, "
+      "major_iter_threshold, mgain, square_joined_channels and spectral_fitter "
+      "(fit(values, x, y), fit_and_evaluate(values, x, y)). With a parallel grid the "
+      "function is called twice per subimage and major iteration: first with "
+      "meta.max_iterations == 0 to find the peak (only 'level' is used), then with the "
+      "configured count and meta.major_iter_threshold set. A tensor kept after the call "
+      "stays readable but its contents are stale.")
       .def_readwrite("filename", &radler::Settings::Python::filename);
   py::class_<radler::Settings::Parallel>(settings, "Parallel")
       .def_readwrite("grid_width", &radler::Settings::Parallel::grid_width)
@@ -1494,4 +1516,5 @@ PYBIND11_MODULE(radler, m) {  // python/pywrappers.cc
   InitTiling(m);
   InitDistributed(m);
   InitFitters(m);
+  radler::python::InitPythonDeconvolution(m);  // after InitGpu: adds to radler.gpu
 }
