@@ -668,7 +668,8 @@ int rdl_fft64_convolve(rdl_fft* f, double* d_image, const void* d_kernel_spectru
  * (rows / columns / rows, each transform held in LDS), replacing rocFFT for
  * the convolutions of multiscale_transforms.cc:9-21 and
  * subminor_loop.cc:195-218. Lengths must be 2^a 3^b 5^c 7^d and fit in LDS
- * (<= 20480 float, <= 10240 double); otherwise RDL_ERR_UNSUPPORTED.
+ * (<= 10240 in either precision: what one workgroup transforms at a time);
+ * otherwise RDL_ERR_UNSUPPORTED.
  * Spectra are (width/2+1) x height complex (float or double) in natural
  * row-major order, like rocFFT's. Inputs and outputs are float images. */
 typedef struct rdl_conv rdl_conv;

@@ -226,8 +226,8 @@ int rdl_conv_create_ex(rdl_session* s, uint32_t width, uint32_t height, int f64,
                 "bad column strategy");
   RDL_ARG_CHECK(width >= 2 && height >= 2, "bad size");
   *out = nullptr;
-  const size_t esz = f64 ? 16 : 8;
-  const size_t max_elems = std::min<size_t>(rdl::kFftLdsBytes / esz, rdl::kMaxWgElems);
+  // the planning arithmetic of this function: lds_fft_plan.h
+  const size_t max_elems = rdl::LdsMaxLength(f64 != 0);
   if (width > max_elems || height > max_elems) {
     rdl::SetError("LDS FFT: size exceeds LDS capacity");
     return RDL_ERR_UNSUPPORTED;
@@ -240,19 +240,12 @@ int rdl_conv_create_ex(rdl_session* s, uint32_t width, uint32_t height, int f64,
   RDL_HIP_CHECK(hipSetDevice(s->device));
   RDL_TRY(rdl::MakeLdsPlan(s, width, c->f64, &c->row_plan, &c->tw_row));
   RDL_TRY(rdl::MakeLdsPlan(s, height, c->f64, &c->col_plan, &c->tw_col));
-  // transforms per workgroup: fill ~64 KiB (float) / the LDS (double) so small
-  // planes still give each workgroup enough work; never more than LDS holds
-  const size_t budget = c->f64 ? rdl::kFftLdsBytes : 64 * 1024;
-  c->row_count = uint32_t(std::max<size_t>(1, std::min<size_t>(budget / (width * esz), 64)));
-  c->col_count = uint32_t(std::max<size_t>(1, std::min<size_t>(budget / (height * esz), 64)));
-  c->row_count = std::min<uint32_t>(c->row_count, uint32_t(max_elems / width));
-  c->col_count = std::min<uint32_t>(c->col_count, uint32_t(max_elems / height));
+  c->row_count = rdl::LdsTransformsPerWorkgroup(width, c->f64);
+  c->col_count = rdl::LdsTransformsPerWorkgroup(height, c->f64);
   // split columns: N = N1 * N2 with N1 the largest divisor <= sqrt(N)
-  uint32_t n1 = 1;
-  for (uint32_t d = 1; uint64_t(d) * d <= height; ++d)
-    if (height % d == 0) n1 = d;
-  const uint32_t n2 = height / n1;
-  const bool can_split = n1 >= 4 && n2 >= 4;
+  const rdl::LdsSplitFactors sf = rdl::ChooseLdsSplit(height, c->f64);
+  const uint32_t n1 = sf.n1, n2 = sf.n2;
+  const bool can_split = sf.can_split;
   // AUTO keeps the single pass: measured on MI355X (tools/bench_fft.py) the
   // split passes are faster only for the shared-spectrum inverse in float
   // (8192^2: 606 vs 909 us) and slower for the fused convolutions
@@ -294,9 +287,7 @@ int rdl_conv_create_ex(rdl_session* s, uint32_t width, uint32_t height, int f64,
     c->sp.n2 = n2;
     RDL_TRY(rdl::MakeLdsPlan(s, n1, c->f64, &c->sp.plan_n1, &c->tw_n1));
     RDL_TRY(rdl::MakeLdsPlan(s, n2, c->f64, &c->sp.plan_n2, &c->tw_n2));
-    // 256-byte row segments, as many as the sub-lengths allow
-    c->sp.cols = std::max<uint32_t>(
-        1, std::min<uint32_t>(c->f64 ? 16 : 32, rdl::kMaxWgElems / (std::max(n1, n2) + 1)));
+    c->sp.cols = sf.cols;
   }
   // RDL_LOG_FFT_PLANS=1: one line per plan (sizes, precision, which kernels)
   static const bool log_plans = [] {
@@ -461,8 +452,19 @@ int ConvolveSubtract(rdl_conv* c, const float* d_image, uint32_t img_w, uint32_t
                 ? rdl_conv_rows_forward_masked(c, d_image, img_w, img_h, ox, oy, d_work,
                                                d_row_mask)
                 : rdl_conv_rows_forward(c, d_image, img_w, img_h, ox, oy, d_work));
+    // The runtime row kernels transform plane rows 2t and 2t + 1 as one
+    // complex row, so the partner of the window's first or last row needs a
+    // spectrum as well: the convolution columns write their window only, and
+    // with a mask the forward rows leave the rows of an all-zero workgroup
+    // as they were. Whatever d_work held there would reach the window's row
+    // through the shared transform's rounding.
+    uint32_t win0 = oy, win_end = oy + img_h;
+    if (!c->fast_rows) {
+      win0 &= ~1u;
+      win_end = std::min(c->height, (win_end + 1) & ~1u);
+    }
     RDL_TRY(rdl_conv_columns_window(c, d_work, d_work, d_kernel, scale, d_row_mask,
-                                    kernel_layout, oy, img_h, kernel_f32));
+                                    kernel_layout, win0, win_end - win0, kernel_f32));
     if (!peak) return rdl_conv_rows_inverse(c, d_work, d_residual, img_w, img_h, ox, oy, 1);
     // rdl_conv_rows_inverse's launch on these plans, with the search
     rdl::ScopedTiming t(c->s, c->f64 ? "conv64_rows" : "conv_rows",

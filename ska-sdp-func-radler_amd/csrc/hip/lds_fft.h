@@ -6,16 +6,11 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "lds_fft_plan.h"  // the planner and its constants
+
 struct rdl_session;
 
 namespace rdl {
-
-constexpr uint32_t kFftMaxPasses = 24;
-constexpr size_t kFftLdsBytes = 160 * 1024;
-
-// Complex elements one workgroup transforms at a time (count x length):
-// bounds the butterflies per thread, hence registers (no spills at 512 threads).
-constexpr uint32_t kMaxWgElems = 10240;
 
 struct LdsPlan {
   uint32_t n;       // transform length

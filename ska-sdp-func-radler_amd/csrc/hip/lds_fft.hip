@@ -18,7 +18,8 @@
 //                    subtracted from the residual.
 //
 // Lengths must be 2^a 3^b 5^c 7^d (every CalculateGoodFFTSize output is) and
-// fit in LDS (160 KiB: 20480 float / 10240 double complex); otherwise
+// fit one workgroup (kMaxWgElems = 10240 complex elements in either precision;
+// in double that is all 160 KiB of LDS); otherwise
 // rdl_conv_create returns RDL_ERR_UNSUPPORTED and callers use rocFFT.
 // Twiddles come from a float64 table (rounded to T for float plans).
 //
@@ -35,11 +36,6 @@
 
 namespace rdl {
 
-#ifndef RDL_FFT_THREADS
-#define RDL_FFT_THREADS 1024
-#endif
-constexpr uint32_t kFftThreads = RDL_FFT_THREADS;
-
 // ---- one Stockham pass over `count` transforms of length n held in LDS
 // (in place: all butterfly inputs are read to registers before the barrier)
 // Not inlined on purpose: with every radix inlined into one kernel the
@@ -51,7 +47,7 @@ __device__ __attribute__((noinline)) void StockhamPass(Cx<T>* buf, uint32_t n,
                                              uint32_t count, uint32_t ns,
                                              const Cx<T>* __restrict__ tw,
                                              uint32_t tid, uint32_t stride) {
-  constexpr uint32_t BPT = (kMaxWgElems / R + kFftThreads - 1) / kFftThreads;
+  constexpr uint32_t BPT = StockhamBpt(R);
   const uint32_t nb = n / R;
   const uint32_t total = nb * count;
   const uint32_t m = n / (ns * R);
@@ -439,45 +435,7 @@ __global__ __launch_bounds__(kFftThreads) void ColumnsSplitB(SplitArgs a,
 }
 
 // ---------------------------------------------------------------- planning
-// Double plans stop at radix 8 and 3: the composite radix-16 / radix-9
-// butterflies hold twice their inputs in registers, which in double spills
-// past the 128 VGPRs a 1024-thread workgroup leaves each wave (the spill
-// traffic showed up as 4-5x the algorithmic HBM writes).
-// Odd radices run first: the first pass writes its outputs R elements apart,
-// and an odd stride spreads a wave's stores over the LDS banks where a
-// power-of-two one piles them on a few (ds_write_b128: 8-way at stride 8).
-bool Factorize(uint32_t n, bool f64, std::vector<uint8_t>& radix) {
-  radix.clear();
-  uint32_t m = n;
-  uint32_t twos = 0;
-  while (m % 2 == 0) {
-    m /= 2;
-    ++twos;
-  }
-  for (uint32_t r : {7u, 5u})
-    while (m % r == 0) {
-      m /= r;
-      radix.push_back(uint8_t(r));
-    }
-  while (!f64 && m % 9 == 0) {
-    m /= 9;
-    radix.push_back(9);
-  }
-  while (m % 3 == 0) {
-    m /= 3;
-    radix.push_back(3);
-  }
-  const uint32_t big2 = f64 ? 3 : 4;
-  while (twos >= big2) {
-    radix.push_back(uint8_t(1u << big2));
-    twos -= big2;
-  }
-  if (twos == 3) radix.push_back(8);
-  if (twos == 2) radix.push_back(4);
-  if (twos == 1) radix.push_back(2);
-  return m == 1 && radix.size() <= kFftMaxPasses;
-}
-
+// (the radix sequence: Factorize, lds_fft_plan.h)
 int MakeLdsPlan(rdl_session* s, uint32_t n, bool f64, LdsPlan* plan, void** tw) {
   std::vector<uint8_t> radix;
   if (!Factorize(n, f64, radix)) {
@@ -640,23 +598,17 @@ int LdsColumnsSplitLaunch(rdl_session* s, const LdsSplit& sp, const LdsPlan& col
   a.n_cols = width / 2 + 1;
   a.ld = a.n_cols;
   a.cols = sp.cols;
-  const uint32_t sub_len = pass_b ? sp.n2 : sp.n1;
-  // elements per workgroup: half the LDS for double (two workgroups per CU
-  // overlap one's loads with the other's transform), the engine's maximum
-  // for float; the padded stride must fit as well
-  const uint32_t target = f64 ? kMaxWgElems / 2 : kMaxWgElems;
-  a.groups = std::max<uint32_t>(1, target / (a.cols * (sub_len + 1)));
-  a.n_groups = pass_b ? sp.n1 : sp.n2;
-  a.groups = std::min(a.groups, a.n_groups);
-  a.col_tiles = (a.n_cols + a.cols - 1) / a.cols;
+  // the tile geometry: PlanLdsSplitPass, lds_fft_plan.h
+  const LdsSplitPass p = PlanLdsSplitPass(sp.n1, sp.n2, sp.cols, f64, width, pass_b);
+  a.groups = p.groups;
+  a.n_groups = p.n_groups;
+  a.col_tiles = p.col_tiles;
   a.tw_n = col_plan.tw;
   a.row_mask = row_mask;
   a.scale = scale;
   a.mode = mode;
-  const uint32_t grid = a.col_tiles * ((a.n_groups + a.groups - 1) / a.groups);
-  const size_t lds = size_t(a.groups) * a.cols * (sub_len + 1) * (f64 ? 16 : 8);
-  return f64 ? ColumnsSplitT<double>(s, a, grid, lds, pass_b, in, out, kern)
-             : ColumnsSplitT<float>(s, a, grid, lds, pass_b, in, out, kern);
+  return f64 ? ColumnsSplitT<double>(s, a, p.grid, p.lds, pass_b, in, out, kern)
+             : ColumnsSplitT<float>(s, a, p.grid, p.lds, pass_b, in, out, kern);
 }
 
 }  // namespace rdl

@@ -67,7 +67,6 @@ NOT_CALLED_DIRECTLY = {
     "rdl_comm_allreduce_max_n": "needs several ranks: tests/test_distributed.py through the host library",
     "rdl_comm_broadcast": "needs several ranks: tests/test_distributed.py through the host library",
     "rdl_comm_rank": "needs several ranks: tests/test_distributed.py through the host library",
-    "rdl_conv_columns_window": "the column pass of rdl_conv_convolve_subtract, which is tested",
     "rdl_fft64_inverse": "the inverse transform of rdl_fft64_convolve, which is tested",
 }
 
