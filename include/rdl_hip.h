@@ -209,6 +209,26 @@ int rdl_scale(rdl_session* s, float* d_dest, size_t n, float alpha);
  * double(dest))); mode 1: dest = float(double(dest) * alpha) (d_a unused). */
 int rdl_axpy_f64(rdl_session* s, float* d_dest, const float* d_a, size_t n,
                  double alpha, int mode);
+
+/* The weighted average of n_sources planes in one pass: what the chain
+ * rdl_memset_zero, one rdl_axpy / rdl_axpy_f64 per plane, rdl_scale /
+ * rdl_axpy_f64(mode 1) computes, bit for bit, for planes that are already in
+ * device memory (ImageSet::LoadAndAverage / LoadAndAveragePsfs over
+ * DeviceImageAccessor sources).
+ * d_dest[i] = finish(acc_G), acc_0 = +0.0f, acc_{k+1} = step(acc_k, src_k[i], w_k),
+ * k in the order given; h_sources: n_sources device pointers (host array).
+ * mode 0 (the rdl_axpy / rdl_scale arithmetic of ImageSet::LoadAndAverage):
+ *   step = fmaf(src, float(w), acc);  finish = acc * float(factor)
+ * mode 1 (the rdl_axpy_f64 arithmetic of LoadAndAveragePsfs):
+ *   step = float(fma(double(src), w, double(acc)));  finish = float(double(acc) * factor)
+ * n_sources == 0 writes finish(+0.0f). d_dest may not overlap a source.
+ * n_sources is unbounded (planes go to the kernel 16 at a time, the running
+ * value kept in d_dest); planes need 4-byte alignment only (16-byte loads
+ * where d_dest and the sources allow). RDL_ERR_ARG: a NULL destination with
+ * n > 0, a NULL source, a mode other than 0 or 1. */
+int rdl_average_planes(rdl_session* s, const float* const* h_sources,
+                       const double* h_weights, uint32_t n_sources, double factor,
+                       int mode, float* d_dest, size_t n);
 /* dest += a (model accumulation, multiscale_algorithm.cc:457-460). */
 int rdl_add(rdl_session* s, float* d_dest, const float* d_a, size_t n);
 

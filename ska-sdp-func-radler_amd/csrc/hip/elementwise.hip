@@ -114,6 +114,69 @@ __global__ __launch_bounds__(256) void BitsDifferKernel(const uint32_t* __restri
 
 __global__ void ClearFlagKernel(uint32_t* flag) { *flag = 0u; }
 
+// rdl_average_planes: the weighted average of up to kAverageChunk source
+// planes in one pass. Pointers and weights travel as kernel arguments; a
+// longer list runs chunk after chunk with the running value kept in dest
+// (both modes round to float at every step, so that changes no bit).
+constexpr uint32_t kAverageChunk = 16;
+constexpr unsigned kAverageThreads = 256;
+constexpr unsigned kAverageMaxBlocks = 1024;  // 4 per CU; the rest by grid stride
+
+struct AverageChunk {
+  const float* src[kAverageChunk];
+  double weight[kAverageChunk];
+  uint32_t count;
+};
+
+template <int kMode>
+__device__ __forceinline__ float AverageStep(float acc, float v, double w) {
+  if (kMode == 0) return __builtin_fmaf(v, float(w), acc);
+  return float(__builtin_fma(double(v), w, double(acc)));
+}
+
+template <int kMode>
+__device__ __forceinline__ float AverageFinish(float acc, double factor) {
+  if (kMode == 0) return acc * float(factor);
+  return float(double(acc) * factor);
+}
+
+// n4: float4 items (n / 4 when dest and every source of the chunk are
+// 16-byte aligned, else 0); elements from 4 * n4 on take the scalar loop.
+template <int kMode>
+__global__ __launch_bounds__(kAverageThreads) void AveragePlanesKernel(
+    AverageChunk chunk, float* dest, size_t n, size_t n4, int first, int last, double factor) {
+  const size_t stride = size_t(gridDim.x) * kAverageThreads;
+  const size_t t = size_t(blockIdx.x) * kAverageThreads + threadIdx.x;
+  float4* dest4 = reinterpret_cast<float4*>(dest);
+  for (size_t i = t; i < n4; i += stride) {
+    float4 acc = first ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : dest4[i];
+#pragma unroll 4
+    for (uint32_t k = 0; k < chunk.count; ++k) {
+      const float4 v = reinterpret_cast<const float4*>(chunk.src[k])[i];
+      const double w = chunk.weight[k];
+      acc.x = AverageStep<kMode>(acc.x, v.x, w);
+      acc.y = AverageStep<kMode>(acc.y, v.y, w);
+      acc.z = AverageStep<kMode>(acc.z, v.z, w);
+      acc.w = AverageStep<kMode>(acc.w, v.w, w);
+    }
+    if (last) {
+      acc.x = AverageFinish<kMode>(acc.x, factor);
+      acc.y = AverageFinish<kMode>(acc.y, factor);
+      acc.z = AverageFinish<kMode>(acc.z, factor);
+      acc.w = AverageFinish<kMode>(acc.w, factor);
+    }
+    dest4[i] = acc;
+  }
+  for (size_t i = n4 * 4 + t; i < n; i += stride) {
+    float acc = first ? 0.0f : dest[i];
+#pragma unroll 4
+    for (uint32_t k = 0; k < chunk.count; ++k)
+      acc = AverageStep<kMode>(acc, chunk.src[k][i], chunk.weight[k]);
+    if (last) acc = AverageFinish<kMode>(acc, factor);
+    dest[i] = acc;
+  }
+}
+
 inline unsigned GridFor(size_t n) {
   return unsigned(std::min<size_t>(8192, std::max<size_t>(1, DivUp(n, 256))));
 }
@@ -188,6 +251,48 @@ int rdl_scale(rdl_session* s, float* d_dest, size_t n, float alpha) {
   if (n == 0) return RDL_OK;
   rdl::ScaleKernel<<<rdl::GridFor(n), 256, 0, s->stream>>>(d_dest, n, alpha);
   RDL_HIP_CHECK(hipGetLastError());
+  return RDL_OK;
+}
+
+int rdl_average_planes(rdl_session* s, const float* const* h_sources,
+                       const double* h_weights, uint32_t n_sources, double factor,
+                       int mode, float* d_dest, size_t n) {
+  RDL_ARG_CHECK(s, "NULL session");
+  RDL_ARG_CHECK(mode == 0 || mode == 1, "rdl_average_planes: mode must be 0 or 1");
+  RDL_ARG_CHECK(n == 0 || d_dest, "rdl_average_planes: NULL destination");
+  RDL_ARG_CHECK(n_sources == 0 || (h_sources && h_weights),
+                "rdl_average_planes: NULL source or weight list");
+  for (uint32_t k = 0; k != n_sources; ++k)
+    RDL_ARG_CHECK(h_sources[k], "rdl_average_planes: NULL source plane");
+  if (n == 0) return RDL_OK;
+  rdl::ScopedTiming t(s, "average_planes", double(n) * 4.0 * (double(n_sources) + 1.0));
+  uint32_t done = 0;
+  do {
+    rdl::AverageChunk chunk{};
+    chunk.count = std::min(rdl::kAverageChunk, n_sources - done);
+    bool aligned = reinterpret_cast<uintptr_t>(d_dest) % 16 == 0;
+    for (uint32_t k = 0; k != chunk.count; ++k) {
+      chunk.src[k] = h_sources[done + k];
+      chunk.weight[k] = h_weights[done + k];
+      aligned = aligned && reinterpret_cast<uintptr_t>(chunk.src[k]) % 16 == 0;
+    }
+    const int first = done == 0;
+    done += chunk.count;
+    const int last = done == n_sources;
+    const size_t n4 = aligned ? n / 4 : 0;
+    // the float4 loop needs DivUp(n4, threads) blocks, the scalar rest
+    // (all of n when unaligned, at most 3 elements otherwise) its own
+    const size_t items = std::max<size_t>(n4, n - n4 * 4);
+    const unsigned grid = unsigned(std::min<size_t>(
+        rdl::kAverageMaxBlocks, rdl::DivUp(items, size_t(rdl::kAverageThreads))));
+    if (mode == 0)
+      rdl::AveragePlanesKernel<0><<<grid, rdl::kAverageThreads, 0, s->stream>>>(
+          chunk, d_dest, n, n4, first, last, factor);
+    else
+      rdl::AveragePlanesKernel<1><<<grid, rdl::kAverageThreads, 0, s->stream>>>(
+          chunk, d_dest, n, n4, first, last, factor);
+    RDL_HIP_CHECK(hipGetLastError());
+  } while (done != n_sources);
   return RDL_OK;
 }
 

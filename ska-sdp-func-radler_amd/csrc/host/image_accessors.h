@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "aocommon_compat.h"
+#include "device_image_accessor.h"
 
 namespace radler::utils {
 

@@ -2,6 +2,8 @@
 // reference's cpp/image_set.cc.
 #include "image_set.h"
 
+#include "image_accessors.h"
+
 #include <cassert>
 #include <cmath>
 #include <stdexcept>
@@ -194,45 +196,99 @@ void ImageSet::LoadAndAverage(bool use_residual_images) {
   // image_set.cc:105-140: sum of weight*image per deconvolution channel and
   // polarization, then *= 1/sum(weights). Accessor loads go through the
   // session's page-locked staging buffer; the arithmetic runs on the device.
+  //
+  // A plane whose contributing images (weight != 0) are all device accessors
+  // is averaged by one rdl_average_planes call on their pointers: no staging,
+  // no zero-fill, the chain's arithmetic bit for bit. Any other plane takes
+  // the chain, with a device source fed to rdl_axpy where it is.
   rdl_session* s = session_->Handle();
-  planes_.buffer->Zero();
   const size_t n = PlaneSize();
-  float* host = static_cast<float*>(session_->PinnedStaging(n * sizeof(float)));
-  gpu::Buffer& staging = session_->Scratch(gpu::Session::kStaging, n * sizeof(float));
-  std::vector<double> averaged_weights(n_images_, 0.0);
-  size_t image_index = 0;
-  for (const std::vector<size_t>& group : table_.DeconvolutionGroups()) {
-    const size_t start = image_index;
-    for (const size_t original_index : group) {
-      image_index = start;
-      for (const WorkTableEntry* e : table_.OriginalGroups()[original_index]) {
-        const std::unique_ptr<aocommon::ImageAccessor>& acc_ptr =
-            use_residual_images ? e->residual_accessor : e->model_accessor;
-        // the reference's test accessor throws std::logic_error on use
-        // (cpp/test/imageaccessor.h, test_image_set.cc:478)
-        if (!acc_ptr)
-          throw std::logic_error(use_residual_images
-                                     ? "ImageSet: entry has no residual accessor"
-                                     : "ImageSet: entry has no model accessor");
-        const aocommon::ImageAccessor& acc = *acc_ptr;
-        if (acc.Width() != width_ || acc.Height() != height_)
-          throw std::runtime_error("ImageSet: accessor size mismatch");
-        acc.Load(host);
-        if (e->image_weight != 0.0) {
-          session_->H2D(staging.Ptr(), host, n * sizeof(float));
-          // AddWithFactor into a zeroed plane
-          gpu::Check(rdl_axpy(s, Data(image_index), staging.F(), n,
-                              float(e->image_weight), 0),
-                     "rdl_axpy");
-          averaged_weights[image_index] += e->image_weight;
+  struct Sources {
+    std::vector<const float*> planes;  // contributing device planes, in order
+    std::vector<double> weights;
+    bool any_device = false, host_contributes = false;
+    bool Fused() const { return any_device && !host_contributes; }
+  };
+  std::vector<Sources> sources(n_images_);
+  const auto for_each_source = [&](auto&& visit) {
+    size_t image_index = 0;
+    for (const std::vector<size_t>& group : table_.DeconvolutionGroups()) {
+      const size_t start = image_index;
+      for (const size_t original_index : group) {
+        image_index = start;
+        for (const WorkTableEntry* e : table_.OriginalGroups()[original_index]) {
+          visit(*e, image_index);
+          ++image_index;
         }
-        ++image_index;
       }
     }
+  };
+  const auto accessor_of = [&](const WorkTableEntry& e) -> const aocommon::ImageAccessor& {
+    const std::unique_ptr<aocommon::ImageAccessor>& acc_ptr =
+        use_residual_images ? e.residual_accessor : e.model_accessor;
+    // the reference's test accessor throws std::logic_error on use
+    // (cpp/test/imageaccessor.h, test_image_set.cc:478)
+    if (!acc_ptr)
+      throw std::logic_error(use_residual_images ? "ImageSet: entry has no residual accessor"
+                                                 : "ImageSet: entry has no model accessor");
+    if (acc_ptr->Width() != width_ || acc_ptr->Height() != height_)
+      throw std::runtime_error("ImageSet: accessor size mismatch");
+    return *acc_ptr;
+  };
+  bool any_fused = false;
+  for_each_source([&](const WorkTableEntry& e, size_t image_index) {
+    Sources& to = sources[image_index];
+    const float* d_plane = DevicePlane(accessor_of(e));
+    if (d_plane) to.any_device = true;
+    if (e.image_weight == 0.0) return;
+    if (d_plane) {
+      to.planes.push_back(d_plane);
+      to.weights.push_back(e.image_weight);
+    } else {
+      to.host_contributes = true;
+    }
+  });
+  for (const Sources& to : sources) any_fused = any_fused || to.Fused();
+  if (!any_fused) {
+    planes_.buffer->Zero();
+  } else {
+    for (size_t i = 0; i != n_images_; ++i)
+      if (!sources[i].Fused()) session_->Zero(Data(i), n * sizeof(float));
   }
-  for (size_t i = 0; i != n_images_; ++i)
-    gpu::Check(rdl_scale(s, Data(i), n, float(1.0 / averaged_weights[i])),
-               "rdl_scale");
+  float* host = nullptr;
+  gpu::Buffer* staging = nullptr;
+  std::vector<double> averaged_weights(n_images_, 0.0);
+  for_each_source([&](const WorkTableEntry& e, size_t image_index) {
+    if (e.image_weight != 0.0) averaged_weights[image_index] += e.image_weight;
+    if (sources[image_index].Fused()) return;
+    const aocommon::ImageAccessor& acc = accessor_of(e);
+    const float* d_plane = DevicePlane(acc);
+    if (!d_plane) {
+      if (!host) {
+        host = static_cast<float*>(session_->PinnedStaging(n * sizeof(float)));
+        staging = &session_->Scratch(gpu::Session::kStaging, n * sizeof(float));
+      }
+      acc.Load(host);
+    }
+    if (e.image_weight != 0.0) {
+      if (!d_plane) {
+        session_->H2D(staging->Ptr(), host, n * sizeof(float));
+        d_plane = staging->F();
+      }
+      // AddWithFactor into a zeroed plane
+      gpu::Check(rdl_axpy(s, Data(image_index), d_plane, n, float(e.image_weight), 0),
+                 "rdl_axpy");
+    }
+  });
+  for (size_t i = 0; i != n_images_; ++i) {
+    const double factor = 1.0 / averaged_weights[i];
+    if (sources[i].Fused())
+      gpu::Check(rdl_average_planes(s, sources[i].planes.data(), sources[i].weights.data(),
+                                    uint32_t(sources[i].planes.size()), factor, 0, Data(i), n),
+                 "rdl_average_planes");
+    else
+      gpu::Check(rdl_scale(s, Data(i), n, float(factor)), "rdl_scale");
+  }
   session_->Sync();
 }
 
@@ -247,25 +303,61 @@ std::vector<gpu::Planes> ImageSet::LoadAndAveragePsfs() const {
     const size_t n = pw * ph;
     gpu::Planes planes =
         gpu::Planes::Make(*session_, pw, ph, NDeconvolutionChannels());
-    planes.buffer->Zero();
-    float* host = static_cast<float*>(session_->PinnedStaging(n * sizeof(float)));
-    gpu::Buffer& staging = session_->Scratch(gpu::Session::kStaging, n * sizeof(float));
+    // a channel whose PSFs are all device accessors (of this plane size): one
+    // rdl_average_planes call; any other the chain, as in LoadAndAverage
+    struct Sources {
+      std::vector<const float*> planes;
+      std::vector<double> weights;
+      bool all_device = true;
+    };
+    std::vector<Sources> sources(NDeconvolutionChannels());
     std::vector<double> averaged(NDeconvolutionChannels(), 0.0);
     for (size_t g = 0; g != NOriginalChannels(); ++g) {
       const size_t ch = (g * NDeconvolutionChannels()) / NOriginalChannels();
       const WorkTableEntry& e = *table_.OriginalGroups()[g].front();
       const aocommon::ImageAccessor& acc = *e.psf_accessors[psf_index];
-      acc.Load(host);
-      session_->H2D(staging.Ptr(), host, n * sizeof(float));
-      gpu::Check(rdl_axpy_f64(s, planes.Plane(ch), staging.F(), n,
-                              e.image_weight, 0),
-                 "rdl_axpy_f64");
+      // (WorkTable::ValidatePsfs requires it of every table Perform sees)
+      if (acc.Width() != pw || acc.Height() != ph)
+        throw std::runtime_error("ImageSet: PSF accessor size mismatch");
+      const float* d_plane = DevicePlane(acc);
+      if (d_plane) {
+        sources[ch].planes.push_back(d_plane);
+        sources[ch].weights.push_back(e.image_weight);
+      } else {
+        sources[ch].all_device = false;
+      }
       averaged[ch] += e.image_weight;
+    }
+    bool any_chain = false;
+    for (const Sources& to : sources) any_chain = any_chain || !to.all_device;
+    if (any_chain) {
+      planes.buffer->Zero();
+      float* host = static_cast<float*>(session_->PinnedStaging(n * sizeof(float)));
+      gpu::Buffer& staging = session_->Scratch(gpu::Session::kStaging, n * sizeof(float));
+      for (size_t g = 0; g != NOriginalChannels(); ++g) {
+        const size_t ch = (g * NDeconvolutionChannels()) / NOriginalChannels();
+        if (sources[ch].all_device) continue;
+        const WorkTableEntry& e = *table_.OriginalGroups()[g].front();
+        const aocommon::ImageAccessor& acc = *e.psf_accessors[psf_index];
+        const float* d_plane = DevicePlane(acc);
+        if (!d_plane) {
+          acc.Load(host);
+          session_->H2D(staging.Ptr(), host, n * sizeof(float));
+          d_plane = staging.F();
+        }
+        gpu::Check(rdl_axpy_f64(s, planes.Plane(ch), d_plane, n, e.image_weight, 0),
+                   "rdl_axpy_f64");
+      }
     }
     for (size_t ch = 0; ch != NDeconvolutionChannels(); ++ch) {
       const double f = averaged[ch] == 0.0 ? 0.0 : 1.0 / averaged[ch];
-      gpu::Check(rdl_axpy_f64(s, planes.Plane(ch), nullptr, n, f, 1),
-                 "rdl_axpy_f64");
+      if (sources[ch].all_device)
+        gpu::Check(rdl_average_planes(s, sources[ch].planes.data(), sources[ch].weights.data(),
+                                      uint32_t(sources[ch].planes.size()), f, 1,
+                                      planes.Plane(ch), n),
+                   "rdl_average_planes");
+      else
+        gpu::Check(rdl_axpy_f64(s, planes.Plane(ch), nullptr, n, f, 1), "rdl_axpy_f64");
     }
     session_->Sync();
     result.push_back(std::move(planes));
@@ -273,16 +365,45 @@ std::vector<gpu::Planes> ImageSet::LoadAndAveragePsfs() const {
   return result;
 }
 
+float* ImageSet::DevicePlane(const aocommon::ImageAccessor& accessor) const {
+  const auto* device = dynamic_cast<const utils::DeviceImageAccessor*>(&accessor);
+  return device && device->Device() == session_->Device() ? device->Data() : nullptr;
+}
+
+void ImageSet::StorePlane(aocommon::ImageAccessor& accessor, const float* d_plane) const {
+  const size_t bytes = PlaneSize() * sizeof(float);
+  if (float* d_dest = DevicePlane(accessor)) {
+    if (!static_cast<const utils::DeviceImageAccessor&>(accessor).Writable())
+      throw std::logic_error("ImageSet: store to a read-only device image");
+    // stream-ordered: Radler::Perform synchronises after the last store
+    session_->D2D(d_dest, d_plane, bytes);
+    return;
+  }
+  float* host = static_cast<float*>(session_->PinnedStaging(bytes));
+  session_->D2H(host, d_plane, bytes);
+  accessor.Store(host);
+}
+
+bool ImageSet::HasDeviceAccessors(const WorkTable& table) {
+  const auto is_device = [](const std::unique_ptr<aocommon::ImageAccessor>& accessor) {
+    return dynamic_cast<const utils::DeviceImageAccessor*>(accessor.get()) != nullptr;
+  };
+  for (const WorkTableEntry& e : table) {
+    if (is_device(e.residual_accessor) || is_device(e.model_accessor)) return true;
+    for (const auto& psf : e.psf_accessors)
+      if (is_device(psf)) return true;
+  }
+  return false;
+}
+
 void ImageSet::AssignAndStoreResidual() {  // image_set.cc:290-307
-  float* host = static_cast<float*>(session_->PinnedStaging(PlaneSize() * sizeof(float)));
   size_t image_index = 0;
   for (const std::vector<size_t>& group : table_.DeconvolutionGroups()) {
     const size_t start = image_index;
     for (const size_t original_index : group) {
       image_index = start;
       for (const WorkTableEntry* e : table_.OriginalGroups()[original_index]) {
-        session_->D2H(host, Data(image_index), PlaneSize() * sizeof(float));
-        e->residual_accessor->Store(host);
+        StorePlane(*e->residual_accessor, Data(image_index));
         ++image_index;
       }
     }
@@ -292,12 +413,10 @@ void ImageSet::AssignAndStoreResidual() {  // image_set.cc:290-307
 void ImageSet::InterpolateAndStoreModel(
     const schaapcommon::fitters::SpectralFitter* fitter, const ForcedTermImages* forced) {
   // image_set.cc:209-288
-  float* host = static_cast<float*>(session_->PinnedStaging(PlaneSize() * sizeof(float)));
   if (NDeconvolutionChannels() == NOriginalChannels()) {
     size_t image_index = 0;
     for (const WorkTableEntry& e : table_) {
-      session_->D2H(host, Data(image_index), PlaneSize() * sizeof(float));
-      e.model_accessor->Store(host);
+      StorePlane(*e.model_accessor, Data(image_index));
       ++image_index;
     }
     return;
@@ -347,8 +466,8 @@ void ImageSet::InterpolateAndStoreModel(
                                              out.F(), PlaneSize()),
                      "rdl_logpoly_interpolate");
         for (size_t g = g0; g != g0 + n_out; ++g) {
-          session_->D2H(host, out.F() + (g - g0) * PlaneSize(), PlaneSize() * sizeof(float));
-          table_.OriginalGroups()[g][p]->model_accessor->Store(host);
+          StorePlane(*table_.OriginalGroups()[g][p]->model_accessor,
+                     out.F() + (g - g0) * PlaneSize());
         }
       }
     }
@@ -362,8 +481,7 @@ void ImageSet::InterpolateAndStoreModel(
       const size_t ch = (g * NDeconvolutionChannels()) / NOriginalChannels();
       const WorkTable::Group& group = table_.OriginalGroups()[g];
       for (size_t p = 0; p != group.size(); ++p) {
-        session_->D2H(host, Data(ch * n_pol_ + p), PlaneSize() * sizeof(float));
-        group[p]->model_accessor->Store(host);
+        StorePlane(*group[p]->model_accessor, Data(ch * n_pol_ + p));
       }
     }
     return;
@@ -390,9 +508,8 @@ void ImageSet::InterpolateAndStoreModel(
                                           uint32_t(n_out), out.F(), PlaneSize()),
                  "rdl_spectral_interpolate");
       for (size_t g = g0; g != g0 + n_out; ++g) {
-        session_->D2H(host, out.F() + (g - g0) * PlaneSize(),
-                      PlaneSize() * sizeof(float));
-        table_.OriginalGroups()[g][p]->model_accessor->Store(host);
+        StorePlane(*table_.OriginalGroups()[g][p]->model_accessor,
+                   out.F() + (g - g0) * PlaneSize());
       }
     }
   }

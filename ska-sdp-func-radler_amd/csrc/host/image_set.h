@@ -83,9 +83,21 @@ class ImageSet {
                                                 std::vector<double>& frequencies,
                                                 std::vector<float>& weights);
 
+  /// Whether any accessor of the table is a DeviceImageAccessor: the caller's
+  /// device memory is then read and written in place, and Radler orders the
+  /// device around it.
+  static bool HasDeviceAccessors(const WorkTable& table);
+
  private:
   void InitializePolFactor();
   void InitializeIndices();
+  /// The plane of `accessor` when it is a DeviceImageAccessor on this set's
+  /// device, else nullptr (the accessor is then used through Load / Store).
+  float* DevicePlane(const aocommon::ImageAccessor& accessor) const;
+  /// One plane to its accessor: a device copy ordered on the session's
+  /// stream for a device accessor (the caller synchronises the session after
+  /// its last store, as Radler::Perform does), D2H and Store() otherwise.
+  void StorePlane(aocommon::ImageAccessor& accessor, const float* d_plane) const;
 
   const WorkTable& table_;
   gpu::Session* session_;

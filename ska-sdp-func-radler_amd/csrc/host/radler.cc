@@ -63,6 +63,36 @@ Radler::Radler(const Settings& settings, const aocommon::Image& psf_image,
   InitializeDeconvolutionAlgorithm(std::move(table));
 }
 
+Radler::Radler(const Settings& settings, const DeviceImage& psf_image,
+               const DeviceImage& residual_image, const DeviceImage& model_image,
+               double beam_size, aocommon::PolarizationEnum polarization)
+    : Radler(settings, beam_size) {
+  if (psf_image.width != settings.trimmed_image_width ||
+      psf_image.height != settings.trimmed_image_height)
+    throw std::runtime_error("Mismatch in PSF image size");
+  if (residual_image.width != settings.trimmed_image_width ||
+      residual_image.height != settings.trimmed_image_height)
+    throw std::runtime_error("Mismatch in residual image size");
+  if (model_image.width != settings.trimmed_image_width ||
+      model_image.height != settings.trimmed_image_height)
+    throw std::runtime_error("Mismatch in model image size");
+  if (!psf_image.data || !residual_image.data || !model_image.data)
+    throw std::runtime_error("Radler: a device image has no data");
+  auto table = std::make_unique<WorkTable>(std::vector<PsfOffset>{}, 1, 1);
+  auto e = std::make_unique<WorkTableEntry>();
+  e->polarization = polarization;
+  e->image_weight = 1.0;
+  const auto accessor = [](const DeviceImage& image, bool writable) {
+    return std::make_unique<utils::DeviceImageAccessor>(image.data, image.width, image.height,
+                                                        image.device, writable);
+  };
+  e->psf_accessors.emplace_back(accessor(psf_image, false));
+  e->residual_accessor = accessor(residual_image, true);
+  e->model_accessor = accessor(model_image, true);
+  table->AddEntry(std::move(e));
+  InitializeDeconvolutionAlgorithm(std::move(table));
+}
+
 Radler::Radler(const Settings& settings, double beam_size)
     : settings_(settings),
       image_width_(settings.trimmed_image_width),
@@ -95,6 +125,8 @@ ComponentList Radler::GetComponentList() const {
   ImageSet model_set(*table_, settings_.squared_joins,
                      settings_.linked_polarizations, image_width_,
                      image_height_, DeviceSession());
+  // the model planes' producer may have used any stream
+  if (has_device_images_) DeviceSession().DeviceSync();
   model_set.LoadAndAverage(false);
   ComponentList list(image_width_, image_height_, model_set);
   list.MergeDuplicates();
@@ -119,6 +151,9 @@ void Radler::Perform(bool& another_iteration_required,
   ImageSet model_set(*table_, settings_.squared_joins,
                      settings_.linked_polarizations, image_width_,
                      image_height_, s);
+  // Foreign device memory is read from here on, and its producer may have
+  // used any stream: the whole device is waited for once.
+  if (has_device_images_) s.DeviceSync();
   {
     prof::Section p("perform.load");
     residual_set.LoadAndAverage(true);
@@ -277,6 +312,8 @@ void Radler::Perform(bool& another_iteration_required,
       parallel_deconvolution_->FirstAlgorithm();
   model_set.InterpolateAndStoreModel(first.HasSpectralFitter() ? &first.Fitter() : nullptr,
                                      first.SpectrallyForcedImages().get());
+  // every store to device images is complete: any stream may consume them
+  if (has_device_images_) s.Sync();
 }
 
 std::unique_ptr<schaapcommon::fitters::SpectralFitter>
@@ -297,6 +334,8 @@ void Radler::InitializeDeconvolutionAlgorithm(
   FreeDeconvolutionAlgorithms();
   table_ = std::move(table);
   if (table_->OriginalGroups().empty()) throw std::runtime_error("Nothing to clean");
+  has_device_images_ = ImageSet::HasDeviceAccessors(*table_);
+  if (has_device_images_) ValidateDeviceImages();
   if (!std::isfinite(beam_size_)) {
     log::Warn() << "No proper beam size available in deconvolution!\n";
     beam_size_ = 0.0;
@@ -431,6 +470,62 @@ void Radler::ReadMask(const WorkTable& group_table) {  // :434-527
     parallel_deconvolution_->SetCleanMask(reinterpret_cast<const bool*>(clean_mask_.data()));
 }
 
+int Radler::DeviceIndex() const {
+  return settings_.gpu_device >= 0 ? settings_.gpu_device : gpu::Session::DefaultDevice();
+}
+
+void Radler::ValidateDeviceImages() const {
+  const int device = DeviceIndex();
+  struct Range {
+    const char* begin;
+    const char* end;
+    std::string name;
+  };
+  std::vector<Range> residuals, models;
+  const auto check = [&](const aocommon::ImageAccessor* accessor, const std::string& name,
+                         bool is_psf, std::vector<Range>* ranges) {
+    const auto* image = dynamic_cast<const utils::DeviceImageAccessor*>(accessor);
+    if (!image) return;
+    std::ostringstream msg;
+    if (image->Device() != device) {
+      msg << "Radler: the " << name << " is on HIP device " << image->Device()
+          << ", the deconvolution runs on device " << device;
+      throw std::runtime_error(msg.str());
+    }
+    if (is_psf) return;  // sizes: WorkTable::ValidatePsfs
+    if (image->Width() != image_width_ || image->Height() != image_height_) {
+      msg << "Radler: the " << name << " is " << image->Width() << " x " << image->Height()
+          << " pixels, the settings give " << image_width_ << " x " << image_height_;
+      throw std::runtime_error(msg.str());
+    }
+    if (!image->Writable()) {
+      msg << "Radler: the " << name << " (device " << image->Device() << ", address "
+          << static_cast<const void*>(image->Data())
+          << ") is read-only, Perform() writes residual and model images";
+      throw std::runtime_error(msg.str());
+    }
+    const char* begin = reinterpret_cast<const char*>(image->Data());
+    ranges->push_back(Range{begin, begin + image->Bytes(), name});
+  };
+  for (const WorkTableEntry& e : *table_) {
+    const std::string of_entry = " image of entry " + std::to_string(e.index);
+    check(e.residual_accessor.get(), "residual" + of_entry, false, &residuals);
+    check(e.model_accessor.get(), "model" + of_entry, false, &models);
+    for (size_t p = 0; p != e.psf_accessors.size(); ++p)
+      check(e.psf_accessors[p].get(), "PSF " + std::to_string(p) + of_entry, true, nullptr);
+  }
+  for (const Range& r : residuals)
+    for (const Range& m : models)
+      if (r.begin < m.end && m.begin < r.end) {
+        std::ostringstream msg;
+        msg << "Radler: the " << r.name << " [" << static_cast<const void*>(r.begin) << ", "
+            << static_cast<const void*>(r.end) << ") overlaps the " << m.name << " ["
+            << static_cast<const void*>(m.begin) << ", " << static_cast<const void*>(m.end)
+            << ") in device memory";
+        throw std::runtime_error(msg.str());
+      }
+}
+
 void Radler::FreeDeconvolutionAlgorithms() {
   parallel_deconvolution_->FreeDeconvolutionAlgorithms();
   table_.reset();
@@ -444,9 +539,7 @@ gpu::Session& Radler::DeviceSession() const {
   // The device is opened on first use, so constructing a Radler (argument
   // validation) needs no GPU; Perform() fails loudly without one.
   if (!session_) {
-    const int device = settings_.gpu_device >= 0 ? settings_.gpu_device
-                                                 : gpu::Session::DefaultDevice();
-    session_ = gpu::Session::ForDevice(device);
+    session_ = gpu::Session::ForDevice(DeviceIndex());
   }
   return *session_;
 }

@@ -9,6 +9,7 @@
 
 #include "aocommon_compat.h"
 #include "component_list.h"
+#include "device_image_accessor.h"
 #include "settings.h"
 #include "spectral_fitter.h"
 #include "work_table.h"
@@ -32,6 +33,15 @@ class Radler {
   /// buffers alive while this object is used.
   Radler(const Settings& settings, const aocommon::Image& psf_image,
          aocommon::Image& residual_image, aocommon::Image& model_image,
+         double beam_size,
+         aocommon::PolarizationEnum polarization =
+             aocommon::PolarizationEnum::StokesI);
+  /// The same for images that already live in device memory: the PSF is read
+  /// and residual and model are read and written where they are, with no
+  /// copy through the host. The planes stay valid, and are not written by
+  /// anyone else during Perform(), while this object is used.
+  Radler(const Settings& settings, const DeviceImage& psf_image,
+         const DeviceImage& residual_image, const DeviceImage& model_image,
          double beam_size,
          aocommon::PolarizationEnum polarization =
              aocommon::PolarizationEnum::StokesI);
@@ -65,6 +75,10 @@ class Radler {
  private:
   Radler(const Settings& settings, double beam_size);
   void InitializeDeconvolutionAlgorithm(std::unique_ptr<WorkTable> table);
+  /// The device accessors of the table against the session's device, the
+  /// image size, writability and each other; std::runtime_error.
+  void ValidateDeviceImages() const;
+  int DeviceIndex() const;
   /// radler.cc:410-432: the term cube of settings.spectral_fitting.forced_filename
   void ReadForcedSpectrumImages();
   /// radler.cc:434-527: settings.fits_mask and the horizon mask
@@ -72,6 +86,7 @@ class Radler {
 
   const Settings settings_;
   std::unique_ptr<WorkTable> table_;
+  bool has_device_images_ = false;  // any DeviceImageAccessor in table_
   mutable std::shared_ptr<gpu::Session> session_;
   std::unique_ptr<algorithms::ParallelDeconvolution> parallel_deconvolution_;
   size_t image_width_ = 0;

@@ -330,13 +330,87 @@ bool InterpreterIsFinalizing() {
 #endif
 }
 
+// The keep-alive of imported planes: gives the tensor back to its producer.
+// The teardown rules of ~PythonDeconvolution: a producer's deleter may touch
+// Python objects, so it runs with the GIL or, once no thread can get the GIL
+// any more, not at all (the memory goes with the process).
+void ReleaseImported(void* pointer) {
+  auto* tensor = static_cast<DLManagedTensor*>(pointer);
+  if (!tensor || !tensor->deleter) return;
+  if (!Py_IsInitialized()) return;
+  if (PyGILState_Check()) {
+    tensor->deleter(tensor);
+    return;
+  }
+  if (InterpreterIsFinalizing()) return;
+  py::gil_scoped_acquire gil;
+  tensor->deleter(tensor);
+}
+
+std::shared_ptr<gpu::Session> ArraySession(const DeviceArray& a) {
+  return gpu::Session::ForDevice(a.device);
+}
+
 }  // namespace
+
+bool IsDlpackObject(const py::handle& object) {
+  return !py::isinstance<py::array>(object) && py::hasattr(object, "__dlpack__");
+}
+
+DeviceImages ImportDeviceImages(const py::object& object, const std::string& argument) {
+  const std::string name = "'" + argument + "'";
+  const std::string rocm = "a ROCm device (DLPack device type " + std::to_string(int(kDLROCM)) + ")";
+  if (!IsDlpackObject(object))
+    throw py::type_error(name + " is a " + TypeName(object) +
+                         ": a float32 numpy array or an object with __dlpack__ on " + rocm +
+                         " is required");
+  if (py::hasattr(object, "__dlpack_device__")) {
+    // asked first: a host tensor is refused without being exported
+    const py::tuple device = object.attr("__dlpack_device__")();
+    if (device.size() != 2 || device[0].cast<int>() != int(kDLROCM))
+      throw py::type_error(name + " is on DLPack device " + std::string(py::str(device)) +
+                           ", not on " + rocm);
+  }
+  py::object capsule = object.attr("__dlpack__")();
+  if (!PyCapsule_IsValid(capsule.ptr(), "dltensor"))
+    throw py::type_error(name + ": its __dlpack__() did not return a 'dltensor' capsule");
+  auto* managed =
+      static_cast<DLManagedTensor*>(PyCapsule_GetPointer(capsule.ptr(), "dltensor"));
+  const DLTensor& t = managed->dl_tensor;
+  // (a refused capsule is still its producer's: its destructor releases it)
+  if (t.device.device_type != kDLROCM)
+    throw py::type_error(name + " is on DLPack device (" +
+                         std::to_string(int(t.device.device_type)) + ", " +
+                         std::to_string(t.device.device_id) + "), not on " + rocm);
+  if (t.dtype.code != kDLFloat || t.dtype.bits != 32 || t.dtype.lanes != 1)
+    throw py::type_error(name + " has dtype (code " + std::to_string(int(t.dtype.code)) + ", " +
+                         std::to_string(int(t.dtype.bits)) + " bits), float32 is required");
+  const size_t ndim = size_t(std::max(t.ndim, 0));
+  const std::vector<int64_t> shape(t.shape, t.shape + ndim);
+  if (t.strides) {
+    const std::vector<int64_t> compact = CompactStrides(shape);
+    for (size_t i = 0; i != ndim; ++i)
+      if (shape[i] > 1 && t.strides[i] != compact[i])
+        throw py::type_error(name + " is not C-contiguous (shape " + ShapeText(shape) +
+                             ", strides " + ShapeText(t.strides, ndim) + " elements)");
+  }
+  if (!t.data && Count(shape) != 0) throw py::type_error(name + " has no data");
+  // consumed from here on: the tensor is the keep-alive's to delete
+  PyCapsule_SetName(capsule.ptr(), "used_dltensor");
+  DeviceImages images;
+  images.keep_alive = std::shared_ptr<void>(static_cast<void*>(managed), &ReleaseImported);
+  images.data = reinterpret_cast<float*>(static_cast<char*>(t.data) + t.byte_offset);
+  images.shape = shape;
+  images.device = t.device.device_id;
+  return images;
+}
 
 void InitPythonDeconvolution(py::module_& m) {
   py::module_ gpu = m.attr("gpu").cast<py::module_>();
   py::class_<DeviceArray>(
       gpu, "DeviceArray",
-      "A float32, C-contiguous view of an image set's own device memory, as passed to "
+      "A float32, C-contiguous array in device memory: radler.gpu.to_device(array), or a view "
+      "of an image set's own memory as passed to "
       "deconvolve_device(residual, model, psf, meta). Use it through DLPack "
       "(torch.from_dlpack(array)): the tensor shares the memory, so residual and model are "
       "edited in place; psf is read-only by contract. The view and every tensor made from "
@@ -349,6 +423,40 @@ void InitPythonDeconvolution(py::module_& m) {
                                return shape;
                              })
       .def_property_readonly("dtype", [](const DeviceArray&) { return "float32"; })
+      .def_property_readonly(
+          "data_ptr", [](const DeviceArray& a) { return reinterpret_cast<uintptr_t>(a.data); },
+          "The device address of the first element.")
+      .def(
+          "numpy",
+          [](const DeviceArray& a) {
+            py::array_t<float> host(std::vector<py::ssize_t>(a.shape.begin(), a.shape.end()));
+            float* h_dst = host.mutable_data();
+            const size_t bytes = Count(a.shape) * sizeof(float);
+            {
+              py::gil_scoped_release release;
+              const std::shared_ptr<gpu::Session> session = ArraySession(a);
+              session->DeviceSync();  // whoever wrote it, on whatever stream
+              if (bytes != 0) session->D2H(h_dst, a.data, bytes);
+              session->Sync();
+            }
+            return host;
+          },
+          "A copy on the host (float32 numpy array), taken after the device has finished "
+          "every queued operation.")
+      .def(
+          "view",
+          [](const DeviceArray& a, size_t offset, const std::vector<int64_t>& shape) {
+            for (int64_t d : shape)
+              if (d < 0) throw std::runtime_error("DeviceArray.view: negative dimension");
+            if (offset > Count(a.shape) || Count(shape) > Count(a.shape) - offset)
+              throw std::runtime_error("DeviceArray.view: " + std::to_string(offset) + " + " +
+                                       ShapeText(shape) + " elements do not fit in " +
+                                       ShapeText(a.shape));
+            return DeviceArray{a.buffer, a.data + offset, shape, a.device};
+          },
+          py::arg("offset"), py::arg("shape"),
+          "A C-contiguous view of `shape` that starts `offset` elements into this array "
+          "(4-byte granularity: the result need not be 16-byte aligned).")
       .def("__dlpack_device__",
            [](const DeviceArray& a) { return py::make_tuple(int(kDLROCM), a.device); })
       .def(
@@ -360,6 +468,30 @@ void InitPythonDeconvolution(py::module_& m) {
             return ExportDlpack(a);
           },
           py::kw_only(), py::arg("stream") = py::none());
+
+  gpu.def(
+      "to_device",
+      [](const py::array_t<float, py::array::c_style>& array, int device) {
+        const std::shared_ptr<gpu::Session> session =
+            gpu::Session::ForDevice(device >= 0 ? device : gpu::Session::DefaultDevice());
+        DeviceArray out;
+        out.shape.assign(array.shape(), array.shape() + array.ndim());
+        out.device = session->Device();
+        const size_t bytes = size_t(array.size()) * sizeof(float);
+        const float* h_src = array.data();
+        {
+          py::gil_scoped_release release;
+          out.buffer = std::make_shared<gpu::Buffer>(*session, std::max<size_t>(bytes, 16));
+          if (bytes != 0) session->H2D(out.buffer->Ptr(), h_src, bytes);
+          session->Sync();
+        }
+        out.data = out.buffer->F();
+        return out;
+      },
+      py::arg("array").noconvert(), py::arg("device") = -1,
+      "A float32 numpy array copied to the device (the process's session of `device`; -1: the "
+      "default device) as a radler.gpu.DeviceArray, which radler.Radler and the WorkTableEntry "
+      "setters accept in place of a numpy array.");
 
   py::module_ helpers = m.def_submodule(
       "python_deconvolution",

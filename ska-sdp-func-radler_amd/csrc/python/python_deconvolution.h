@@ -21,6 +21,7 @@
 
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "deconvolution_algorithm.h"
 
@@ -51,6 +52,27 @@ class PythonDeconvolution final : public DeconvolutionAlgorithm {
 }  // namespace radler::algorithms
 
 namespace radler::python {
+
+/// Planes in the caller's device memory, imported over DLPack: what a
+/// DeviceImageAccessor is made of. `keep_alive` owns the consumed
+/// DLManagedTensor; its deleter runs when the last copy is released (with
+/// the GIL, when the interpreter is still there to give it).
+struct DeviceImages {
+  std::shared_ptr<void> keep_alive;
+  float* data = nullptr;
+  std::vector<int64_t> shape;
+  int device = 0;
+};
+
+/// An object that is not a numpy array and has __dlpack__: a candidate for
+/// ImportDeviceImages.
+bool IsDlpackObject(const pybind11::handle& object);
+
+/// Consumes object.__dlpack__(). The tensor must be on a ROCm device, float32
+/// and C-contiguous (byte_offset is honoured); pybind11::type_error naming
+/// `argument` and the failed requirement otherwise. The shape is the caller's
+/// to check.
+DeviceImages ImportDeviceImages(const pybind11::object& object, const std::string& argument);
 
 /// radler.gpu.DeviceArray and the radler.python_deconvolution helper classes
 /// (Channel, MetaData, SpectralFitter), registered once; sets the host

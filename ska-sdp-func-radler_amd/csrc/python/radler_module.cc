@@ -37,13 +37,80 @@ namespace {
 
 using FloatArray = py::array_t<float, py::array::c_style>;
 
-template <class T>
-std::unique_ptr<T> MakeAccessor(FloatArray& data) {
-  if (data.ndim() != 2)
-    throw std::runtime_error("Provided array should have 2 dimensions.");
-  aocommon::Image view(data.mutable_data(), size_t(data.shape(1)),
-                       size_t(data.shape(0)));
-  return std::make_unique<T>(view);
+/// A plane argument of the Python API: a float32 numpy array (the host path,
+/// as ever) or an object with __dlpack__ on a ROCm device (planes that stay
+/// where they are: DeviceImageAccessor).
+struct PlaneStack {
+  FloatArray host;
+  radler::python::DeviceImages device;
+  bool on_device = false;
+  std::vector<int64_t> shape;
+
+  std::unique_ptr<aocommon::ImageAccessor> Accessor(size_t index, size_t width, size_t height,
+                                                    bool writable) {
+    const size_t plane = width * height;
+    if (on_device)
+      return std::make_unique<radler::utils::DeviceImageAccessor>(
+          device.data + index * plane, width, height, device.device, writable,
+          device.keep_alive);
+    aocommon::Image view(host.mutable_data() + index * plane, width, height);
+    if (writable) return std::make_unique<radler::utils::LoadAndStoreImageAccessor>(view);
+    return std::make_unique<radler::utils::LoadOnlyImageAccessor>(view);
+  }
+};
+
+std::string ShapeText(const std::vector<int64_t>& shape) {
+  std::ostringstream s;
+  s << '(';
+  for (size_t i = 0; i != shape.size(); ++i) s << (i ? ", " : "") << shape[i];
+  s << ')';
+  return s.str();
+}
+
+/// `convert`: a numpy array of another layout or a safely castable dtype is
+/// copied (the WorkTableEntry setters always did); without it the array must
+/// be float32 and C-contiguous already (the Radler constructor).
+PlaneStack ReadPlanes(const py::object& object, const std::string& argument, bool convert) {
+  PlaneStack planes;
+  if (radler::python::IsDlpackObject(object)) {
+    planes.device = radler::python::ImportDeviceImages(object, argument);
+    planes.on_device = true;
+    planes.shape = planes.device.shape;
+    return planes;
+  }
+  bool is_array = false;  // (a default array_t is an empty array, not a null one)
+  if (convert) {
+    FloatArray converted = FloatArray::ensure(object);
+    if (converted) {
+      planes.host = std::move(converted);
+      is_array = true;
+    } else {
+      PyErr_Clear();
+    }
+  } else if (FloatArray::check_(object)) {
+    planes.host = py::reinterpret_borrow<FloatArray>(object);
+    is_array = true;
+  }
+  if (!is_array)
+    throw py::type_error("'" + argument + "' is a " + Py_TYPE(object.ptr())->tp_name +
+                         " that is no float32 C-contiguous numpy array: such an array, or an "
+                         "object with __dlpack__ on a ROCm device (radler.gpu.DeviceArray, a "
+                         "torch tensor), is required");
+  planes.shape.assign(planes.host.shape(), planes.host.shape() + planes.host.ndim());
+  return planes;
+}
+
+/// One 2-D plane for a WorkTableEntry setter.
+std::unique_ptr<aocommon::ImageAccessor> EntryAccessor(const py::object& object,
+                                                       const std::string& argument,
+                                                       bool writable) {
+  PlaneStack planes = ReadPlanes(object, argument, true);
+  if (planes.shape.size() != 2) {
+    if (!planes.on_device) throw std::runtime_error("Provided array should have 2 dimensions.");
+    throw std::runtime_error("'" + argument + "' has shape " + ShapeText(planes.shape) +
+                             ", a 2-D (height, width) image is required");
+  }
+  return planes.Accessor(0, size_t(planes.shape[1]), size_t(planes.shape[0]), writable);
 }
 
 void InitSettings(py::module& m) {  // python/pysettings.cc
@@ -148,7 +215,9 @@ void InitSettings(py::module& m) {  // python/pysettings.cc
       "function is called twice per subimage and major iteration: first with "
       "meta.max_iterations == 0 to find the peak (only 'level' is used), then with the "
       "configured count and meta.major_iter_threshold set. A tensor kept after the call "
-      "stays readable but its contents are stale.")
+      "stays readable but its contents are stale. The images given to radler.Radler itself "
+      "may be numpy arrays or device arrays (radler.gpu.DeviceArray, torch tensors): the "
+      "function sees the image sets either way.")
       .def_readwrite("filename", &radler::Settings::Python::filename);
   py::class_<radler::Settings::Parallel>(settings, "Parallel")
       .def_readwrite("grid_width", &radler::Settings::Parallel::grid_width)
@@ -301,8 +370,8 @@ void InitIo(py::module& m) {
 void InitWorkTable(py::module& m) {  // python/pywork_table.cc
   py::class_<AccessorList>(m, "VectorUniquePtrImageAccessor")
       .def("__len__", [](const AccessorList& self) { return self.size(); })
-      .def("append", [](AccessorList& self, FloatArray& psf) {
-        self.emplace_back(MakeAccessor<radler::utils::LoadOnlyImageAccessor>(psf));
+      .def("append", [](AccessorList& self, const py::object& psf) {
+        self.emplace_back(EntryAccessor(psf, "psf", false));
       });
 
   py::class_<radler::WorkTable>(m, "WorkTable")
@@ -371,19 +440,30 @@ void InitWorkTable(py::module& m) {  // python/pywork_table.cc
           },
           py::return_value_policy::reference)
       .def_property("residual", nullptr,
-                    [](radler::WorkTableEntry& self, FloatArray& residual) {
-                      self.residual_accessor =
-                          MakeAccessor<radler::utils::LoadAndStoreImageAccessor>(residual);
+                    [](radler::WorkTableEntry& self, const py::object& residual) {
+                      self.residual_accessor = EntryAccessor(residual, "residual", true);
                     })
       .def_property("model", nullptr,
-                    [](radler::WorkTableEntry& self, FloatArray& model) {
-                      self.model_accessor =
-                          MakeAccessor<radler::utils::LoadAndStoreImageAccessor>(model);
+                    [](radler::WorkTableEntry& self, const py::object& model) {
+                      self.model_accessor = EntryAccessor(model, "model", true);
                     });
 }
 
 void InitRadler(py::module& m) {  // python/pyradler.cc
-  py::class_<radler::Radler>(m, "Radler")
+  py::class_<radler::Radler>(
+      m, "Radler",
+      "Radler(settings, work_table, beam_size) or Radler(settings, psf, residual, model, "
+      "beam_size, n_deconvolution_groups=0, frequencies=[], weights=[], polarization=I).\n"
+      "psf, residual and model are, each independently, a float32 C-contiguous numpy array "
+      "or an object with __dlpack__ / __dlpack_device__ on a ROCm device: a "
+      "radler.gpu.DeviceArray (radler.gpu.to_device(array)) or a torch tensor, float32, "
+      "C-contiguous, of shape (height, width) or (n_images, height, width). The "
+      "WorkTableEntry setters (psfs.append, residual, model) accept the same. perform() "
+      "reads device images where they are and writes residual and model back into them; "
+      "nothing is copied through the host and nothing is reallocated. The Radler holds the "
+      "device memory until it is destroyed, so the caller may drop its references. "
+      "perform() waits for the whole device before its first read and for its own work "
+      "before it returns: no stream argument is needed on either side.")
       .def(py::init([](const radler::Settings& settings,
                        radler::WorkTable& work_table, double beam_size) {
              if (settings.thread_count == 0)
@@ -393,24 +473,32 @@ void InitRadler(py::module& m) {  // python/pyradler.cc
                  beam_size);
            }),
            py::arg("settings"), py::arg("work_table"), py::arg("beam_size"))
-      .def(py::init([](const radler::Settings& settings, FloatArray& psf,
-                       FloatArray& residual, FloatArray& model, double beam_size,
-                       size_t n_deconvolution_groups, py::array_t<double>& frequencies,
-                       py::array_t<double>& weights,
+      // psf, residual and model: numpy arrays or device arrays, each on its own
+      .def(py::init([](const radler::Settings& settings, const py::object& psf_object,
+                       const py::object& residual_object, const py::object& model_object,
+                       double beam_size, size_t n_deconvolution_groups,
+                       py::array_t<double>& frequencies, py::array_t<double>& weights,
                        aocommon::PolarizationEnum polarization) {
              if (settings.thread_count == 0)
                throw std::runtime_error("Number of threads should be > 0.");
-             if (psf.ndim() != residual.ndim() || psf.ndim() != model.ndim())
+             PlaneStack psf = ReadPlanes(psf_object, "psf", false);
+             PlaneStack residual = ReadPlanes(residual_object, "residual", false);
+             PlaneStack model = ReadPlanes(model_object, "model", false);
+             if (psf.shape.size() != residual.shape.size() ||
+                 psf.shape.size() != model.shape.size())
                throw std::runtime_error(
                    "Provided arrays should have equal dimension count.");
-             for (py::ssize_t d = 0; d < psf.ndim(); ++d)
-               if (residual.shape(d) != psf.shape(d) || model.shape(d) != psf.shape(d))
-                 throw std::runtime_error("Provided arrays should have equal shape.");
-             if (psf.ndim() != 2 && psf.ndim() != 3)
+             if (residual.shape != psf.shape || model.shape != psf.shape)
+               throw std::runtime_error(
+                   "Provided arrays should have equal shape: psf " + ShapeText(psf.shape) +
+                   ", residual " + ShapeText(residual.shape) + ", model " +
+                   ShapeText(model.shape) + ".");
+             const size_t ndim = psf.shape.size();
+             if (ndim != 2 && ndim != 3)
                throw std::runtime_error("Provided arrays should have 2 or 3 dimensions.");
-             const size_t height = psf.shape(psf.ndim() - 2);
-             const size_t width = psf.shape(psf.ndim() - 1);
-             const size_t n_images = psf.ndim() == 2 ? 1 : psf.shape(0);
+             const size_t height = size_t(psf.shape[ndim - 2]);
+             const size_t width = size_t(psf.shape[ndim - 1]);
+             const size_t n_images = ndim == 2 ? 1 : size_t(psf.shape[0]);
              if (settings.spectral_fitting.mode !=
                      schaapcommon::fitters::SpectralFittingMode::kNoFitting &&
                  frequencies.size() == 0)
@@ -426,11 +514,7 @@ void InitRadler(py::module& m) {  // python/pyradler.cc
                throw std::runtime_error("Provided weights should have shape (n_images).");
              auto table = std::make_unique<radler::WorkTable>(
                  std::vector<radler::PsfOffset>{}, n_images, n_deconvolution_groups);
-             const size_t plane = width * height;
              for (size_t i = 0; i < n_images; ++i) {
-               aocommon::Image p(psf.mutable_data() + i * plane, width, height);
-               aocommon::Image r(residual.mutable_data() + i * plane, width, height);
-               aocommon::Image mo(model.mutable_data() + i * plane, width, height);
                auto e = std::make_unique<radler::WorkTableEntry>();
                if (frequencies.size() > 0) {
                  auto u = frequencies.unchecked<2>();
@@ -440,23 +524,27 @@ void InitRadler(py::module& m) {  // python/pyradler.cc
                e->polarization = polarization;
                e->original_channel_index = i;
                e->image_weight = weights.size() > 0 ? weights.unchecked<1>()(i) : 1.0;
-               e->psf_accessors.emplace_back(
-                   std::make_unique<radler::utils::LoadOnlyImageAccessor>(p));
-               e->residual_accessor =
-                   std::make_unique<radler::utils::LoadAndStoreImageAccessor>(r);
-               e->model_accessor =
-                   std::make_unique<radler::utils::LoadAndStoreImageAccessor>(mo);
+               e->psf_accessors.emplace_back(psf.Accessor(i, width, height, false));
+               e->residual_accessor = residual.Accessor(i, width, height, true);
+               e->model_accessor = model.Accessor(i, width, height, true);
                table->AddEntry(std::move(e));
              }
              return std::make_unique<radler::Radler>(settings, std::move(table),
                                                      beam_size);
            }),
-           py::arg("settings"), py::arg("psf").noconvert(),
-           py::arg("residual").noconvert(), py::arg("model").noconvert(),
+           py::arg("settings"), py::arg("psf"), py::arg("residual"), py::arg("model"),
            py::arg("beam_size"), py::arg("n_deconvolution_groups") = 0,
            py::arg("frequencies") = py::array_t<double>(),
            py::arg("weights") = py::array_t<double>(),
-           py::arg("polarization") = aocommon::PolarizationEnum::StokesI)
+           py::arg("polarization") = aocommon::PolarizationEnum::StokesI,
+           "psf, residual and model, each independently: a float32 C-contiguous numpy array "
+           "of shape (height, width) or (n_images, height, width), or an object with "
+           "__dlpack__ / __dlpack_device__ on a ROCm device of that shape "
+           "(radler.gpu.DeviceArray from radler.gpu.to_device, a torch tensor). Device "
+           "planes are read where they are, and residual and model are written back into "
+           "them by perform(), with no copy through the host; the Radler keeps them alive. "
+           "perform() waits for the whole device before it reads them and for its own "
+           "stream before it returns, so any stream may produce and consume them.")
       .def("perform",
            [](radler::Radler& self, size_t major_iteration_number) {
              py::gil_scoped_release release;
