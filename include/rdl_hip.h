@@ -138,8 +138,10 @@ typedef struct {
 /* Replaces math::peak_finder::Find / Avx<bool> / Simple / FindWithMask
  * (cpp/math/peak_finder.h:80-127, peak_finder.cc:19-56, 97-131, 199-253).
  * Box x in [h_border, w-h_border), y in [max(start_y,v_border),
- * min(end_y,h-v_border)); strict '>' from FLT_MIN, first row-major index on
- * ties, NaN never selected, value = signed pixel. d_mask (uint8, may be NULL)
+ * min(end_y,h-v_border)), intersected with the image: a border or start_y
+ * beyond the image (where the reference's unsigned bounds wrap and it reads
+ * past the image) leaves an empty box. Strict '>' from FLT_MIN, first
+ * row-major index on ties, NaN never selected, value = signed pixel. d_mask (uint8, may be NULL)
  * selects FindWithMask. avx_semantics=1 reproduces the x86 default Avx<>
  * path: with no qualifying pixel it returns (0,0) and image[0] as found. */
 int rdl_find_peak(rdl_session* s, const float* d_image, uint32_t width,

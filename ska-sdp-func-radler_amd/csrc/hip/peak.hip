@@ -10,6 +10,7 @@
 #include <cfloat>
 #include <cstdlib>
 
+#include "conv_peak_box.h"
 #include "rdl_internal.h"
 
 namespace rdl {
@@ -139,17 +140,17 @@ int LaunchFindPeak(rdl_session* s, const float* d_image, uint32_t width,
   a.mask = d_mask;
   a.width = width;
   a.height = height;
-  // peak_finder.cc:27-32 (unsigned wrap-around as in the reference)
-  a.xs = h_border;
-  a.xe = width - h_border;
-  a.ys = start_y > v_border ? start_y : v_border;
-  a.ye = end_y < height - v_border ? end_y : height - v_border;
-  if (a.xe < a.xs) a.xe = a.xs;
-  if (a.ye < a.ys) a.ye = a.ys;
-  if (a.xe > width) a.xe = width;
-  if (a.ye > height) a.ye = height;
+  // peak_finder.cc:27-32, intersected with the image: a border or start_y
+  // beyond it leaves an empty box, never ye < ys (whose `rows` would wrap) or
+  // an xs near 2^32 (whose `xs + threadIdx.x` would)
+  const PeakBox box = MakeSearchBox(width, height, start_y, end_y, h_border, v_border);
+  a.xs = box.xs;
+  a.xe = box.xe;
+  a.ys = box.ys;
+  a.ye = box.ye;
   a.allow_negative = allow_negative;
-  const uint32_t rows = a.ye - a.ys;
+  // a box without columns launches no search either
+  const uint32_t rows = a.xe == a.xs ? 0 : a.ye - a.ys;
   const uint32_t target_blocks = 2048;
   a.rows_per_block = rows == 0 ? 1 : (rows + target_blocks - 1) / target_blocks;
   const uint32_t blocks =
