@@ -535,6 +535,75 @@ int rdl_hogbom_run(rdl_session* s, float* d_residuals, float* d_models,
                    rdl_hogbom_result* out, uint32_t* h_trace,
                    uint64_t trace_cap);
 
+/* ------------------------------------------------- Högbom, a stack of planes */
+/* What the planes of one batch share. Plane b of a stack lies at
+ * base + b * stride (strides in elements, >= width * height). A PSF or mask
+ * stride of 0 means one plane shared by every item; d_mask NULL: no mask. */
+typedef struct {
+  uint32_t width, height;  /* width * height <= RDL_HOGBOM_BATCH_MAX_PIXELS */
+  uint32_t n_planes;       /* B >= 1 */
+  uint32_t flags;          /* RDL_HOGBOM_BATCH_* */
+  float* d_residuals;
+  size_t residual_stride;
+  float* d_models;
+  size_t model_stride;
+  const float* d_psfs;
+  size_t psf_stride;
+  const uint8_t* d_mask;
+  size_t mask_stride;
+  float gain;              /* minor loop gain */
+  float major_loop_gain;
+  float divergence_limit;
+  int32_t allow_negative, stop_on_negative;
+  uint32_t h_border, v_border;
+} rdl_hogbom_batch_params;
+
+typedef struct {
+  rdl_hogbom_result result; /* what rdl_hogbom_run gives for this plane */
+  rdl_peak start;           /* what rdl_find_peak gave before the loop */
+  float first_threshold;    /* the threshold the loop ran with */
+  uint32_t reserved;
+} rdl_hogbom_batch_out;
+
+#define RDL_HOGBOM_BATCH_MAX_PIXELS (1u << 20)
+/* flags: before its start peak is searched, every -0.0f of an active plane's
+ * residual and model becomes +0.0f: what ImageSet::LoadAndAverage's
+ * 0 + 1 * x makes of a plane it loads (radler::PlaneBatch sets it) */
+#define RDL_HOGBOM_BATCH_LOAD_RULE 1u
+
+/* B independent single-image Högbom cleans of the same size, one workgroup
+ * per plane, no launch and no host round trip per component.
+ * For every plane b with h_active[b] != 0 the residual plane, the model
+ * plane, the trace and h_out[b] are bit for bit those of
+ *   rdl_find_peak(plane, 0, height, h_border, v_border, allow_negative,
+ *                 mask, avx_semantics 1)                       -> start
+ *   initial_max = |start.value|
+ *   first_threshold = max(h_threshold[b], initial_max * (1.0f - major_loop_gain))
+ *                     in float, as generic_clean.cc:138-142 with
+ *                     MajorIterationThreshold() = 0
+ *   rdl_hogbom_run(n_images 1, the identity integration, no fit, no RMS
+ *                  image, threshold first_threshold, that start peak,
+ *                  h_iteration_start[b], h_max_iterations[b])  -> result
+ * on that plane alone (with RDL_HOGBOM_BATCH_LOAD_RULE: on that plane with its
+ * -0.0f pixels, and its model's, replaced by +0.0f). A plane with
+ * h_active[b] == 0 is neither read nor
+ * written and h_out[b] and its trace rows are left as given. h_trace (may be
+ * NULL) holds trace_cap (x, y) pairs per plane, plane b's from
+ * h_trace + b * 2 * trace_cap, under rdl_hogbom_run's rules. The per-plane
+ * arrays are host arrays of n_planes entries. One launch runs a bounded
+ * number of components per plane (RDL_HOGBOM_BATCH_CHUNK in the environment
+ * overrides it); the planes not done are launched again, which changes no
+ * bit. RDL_ERR_ARG, before the first device call: a NULL argument other than
+ * d_mask and h_trace, n_planes == 0, an empty plane or one of more than
+ * RDL_HOGBOM_BATCH_MAX_PIXELS pixels, a residual or model stride below
+ * width * height, a PSF or mask stride below it other than 0, an unknown
+ * flag. */
+int rdl_hogbom_batch_run(rdl_session* s, const rdl_hogbom_batch_params* p,
+                         const float* h_threshold, const uint64_t* h_iteration_start,
+                         const uint64_t* h_max_iterations, const uint8_t* h_active,
+                         rdl_hogbom_batch_out* h_out, uint32_t* h_trace,
+                         uint64_t trace_cap);
+
 /* ------------------------------------------------------- sub-minor loop */
 typedef struct {
   uint32_t width, height;  /* image size (psf size equals image size) */

@@ -15,30 +15,11 @@
 // state and the next component's factors. Loop control lives in device
 // memory, so the host enqueues batches of iterations without synchronising;
 // launches after the loop ended return immediately.
-#include "rdl_internal.h"
+#include "hogbom_shared.h"
 #include "logpoly.h"
+#include "rdl_internal.h"
 
 namespace rdl {
-
-struct Window {
-  uint32_t x0, x1, y0, y1;  // image coordinates, half-open
-  int32_t off_x, off_y;     // psf(x - off_x, y - off_y)
-};
-
-__host__ __device__ inline Window SubtractWindow(uint32_t width,
-                                                 uint32_t height, uint32_t x,
-                                                 uint32_t y) {
-  Window w;
-  w.off_x = int32_t(x) - int32_t(width / 2);
-  w.off_y = int32_t(y) - int32_t(height / 2);
-  w.x0 = w.off_x > 0 ? uint32_t(w.off_x) : 0u;
-  w.y0 = w.off_y > 0 ? uint32_t(w.off_y) : 0u;
-  w.x1 = x + width / 2;
-  if (w.x1 > width) w.x1 = width;
-  w.y1 = y + height / 2;
-  if (w.y1 > height) w.y1 = height;
-  return w;
-}
 
 __global__ __launch_bounds__(256) void SubtractKernel(float* image,
                                                       const float* psf,
@@ -55,18 +36,6 @@ __global__ __launch_bounds__(256) void SubtractKernel(float* image,
 }
 
 // ---------------------------------------------------------------- Högbom
-struct HogbomState {
-  uint64_t iteration;
-  uint64_t first_iteration;
-  uint32_t done;
-  uint32_t peak_index;
-  float peak_value;
-  int32_t found;
-  int32_t diverging;
-  uint32_t pad;
-  float factors[RDL_MAX_IMAGES];
-};
-
 struct HogbomArgs {
   float* residuals;
   float* models;

@@ -26,6 +26,7 @@
 #include "fft_sizes.h"
 #include "host_profile.h"
 #include "multiscale_transforms.h"
+#include "plane_batch.h"
 #include "python_deconvolution.h"
 #include "subminor.h"
 
@@ -573,6 +574,118 @@ void InitRadler(py::module& m) {  // python/pyradler.cc
         }
         return sizes;
       });
+}
+
+// radler::PlaneBatch with the Python objects whose memory it works on
+struct PyPlaneBatch {
+  std::unique_ptr<radler::PlaneBatch> batch;
+  py::object psfs, residuals, models;  // the numpy stacks (device stacks: keep_alive)
+};
+
+radler::PlaneBatch::Planes BatchPlanes(PlaneStack& stack, size_t first_dim, size_t height,
+                                       size_t width) {
+  radler::PlaneBatch::Planes planes;
+  planes.on_device = stack.on_device;
+  planes.device = stack.device.device;
+  planes.keep_alive = stack.device.keep_alive;
+  float* base = stack.on_device ? stack.device.data : stack.host.mutable_data();
+  for (size_t b = 0; b != first_dim; ++b) planes.planes.push_back(base + b * height * width);
+  return planes;
+}
+
+void InitPlaneBatch(py::module& m) {
+  py::class_<PyPlaneBatch>(
+      m, "PlaneBatch",
+      "PlaneBatch(settings, psfs, residuals, models, masks=None): B independent planes of one "
+      "size, each cleaned as radler.Radler would clean it alone (algorithm_type generic_clean, "
+      "generic.use_sub_minor_optimization False), all in one launch per perform(). residuals "
+      "and models are (B, height, width) stacks, psfs (height, width) or (B, height, width): "
+      "float32 C-contiguous numpy arrays, or objects with __dlpack__ on a ROCm device "
+      "(radler.gpu.to_device, a torch tensor); residuals and models are updated in place. "
+      "masks: None, or a bool or uint8 numpy array of shape (height, width) or (B, height, "
+      "width), non-zero where a component may be placed. A setting the batch does not honour "
+      "raises RuntimeError naming it.")
+      .def(py::init([](const radler::Settings& settings, const py::object& psfs_object,
+                       const py::object& residuals_object, const py::object& models_object,
+                       const py::object& masks_object) {
+             PlaneStack psfs = ReadPlanes(psfs_object, "psfs", false);
+             PlaneStack residuals = ReadPlanes(residuals_object, "residuals", false);
+             PlaneStack models = ReadPlanes(models_object, "models", false);
+             if (residuals.shape.size() != 3)
+               throw std::runtime_error("'residuals' has shape " + ShapeText(residuals.shape) +
+                                        ", a (B, height, width) stack is required");
+             if (models.shape != residuals.shape)
+               throw std::runtime_error("'models' has shape " + ShapeText(models.shape) +
+                                        ", 'residuals' " + ShapeText(residuals.shape));
+             const size_t n_planes = size_t(residuals.shape[0]);
+             const size_t height = size_t(residuals.shape[1]), width = size_t(residuals.shape[2]);
+             const std::vector<int64_t> plane_shape(residuals.shape.begin() + 1,
+                                                    residuals.shape.end());
+             if (psfs.shape != plane_shape && psfs.shape != residuals.shape)
+               throw std::runtime_error("'psfs' has shape " + ShapeText(psfs.shape) + ", " +
+                                        ShapeText(plane_shape) + " or " +
+                                        ShapeText(residuals.shape) + " is required");
+             if (width != settings.trimmed_image_width || height != settings.trimmed_image_height)
+               throw std::runtime_error(
+                   "The stacks have planes of " + std::to_string(width) + " x " +
+                   std::to_string(height) + " pixels, the settings give " +
+                   std::to_string(settings.trimmed_image_width) + " x " +
+                   std::to_string(settings.trimmed_image_height));
+             py::array_t<uint8_t, py::array::c_style> masks;
+             std::vector<const uint8_t*> mask_planes;
+             if (!masks_object.is_none()) {
+               const py::array given = py::array::ensure(masks_object);
+               if (!given || (given.dtype().kind() != 'b' &&
+                              !(given.dtype().kind() == 'u' && given.itemsize() == 1)))
+                 throw py::type_error("'masks' must be a bool or uint8 numpy array");
+               masks = py::array_t<uint8_t, py::array::c_style>::ensure(
+                   given.dtype().kind() == 'b' ? py::object(given.attr("view")("uint8"))
+                                               : py::object(given));
+               const std::vector<int64_t> shape(masks.shape(), masks.shape() + masks.ndim());
+               if (shape != plane_shape && shape != residuals.shape)
+                 throw std::runtime_error("'masks' has shape " + ShapeText(shape) + ", " +
+                                          ShapeText(plane_shape) + " or " +
+                                          ShapeText(residuals.shape) + " is required");
+               const size_t n_masks = shape.size() == 2 ? 1 : n_planes;
+               for (size_t b = 0; b != n_masks; ++b)
+                 mask_planes.push_back(masks.data() + b * width * height);
+             }
+             auto self = std::make_unique<PyPlaneBatch>();
+             self->batch = std::make_unique<radler::PlaneBatch>(
+                 settings, BatchPlanes(psfs, psfs.shape.size() == 2 ? 1 : n_planes, height, width),
+                 BatchPlanes(residuals, n_planes, height, width),
+                 BatchPlanes(models, n_planes, height, width), mask_planes);
+             if (!psfs.on_device) self->psfs = psfs.host;
+             if (!residuals.on_device) self->residuals = residuals.host;
+             if (!models.on_device) self->models = models.host;
+             return self;
+           }),
+           py::arg("settings"), py::arg("psfs"), py::arg("residuals"), py::arg("models"),
+           py::arg("masks") = py::none())
+      .def("perform",
+           [](PyPlaneBatch& self, size_t major_iteration_number) {
+             std::vector<bool> another;
+             {
+               py::gil_scoped_release release;
+               self.batch->Perform(another, major_iteration_number);
+             }
+             py::array_t<bool> flags(another.size());
+             for (size_t b = 0; b != another.size(); ++b) flags.mutable_data()[b] = another[b];
+             return flags;
+           },
+           py::arg("major_iteration_number"),
+           "Cleans every plane (first call) or the planes whose flag the call before returned "
+           "True; returns the (B,) bool array of Radler.perform's answers, False for the planes "
+           "left out.")
+      .def_property_readonly("iteration_numbers",
+                             [](const PyPlaneBatch& self) {
+                               const std::vector<size_t>& it = self.batch->IterationNumbers();
+                               py::array_t<uint64_t> out(it.size());
+                               std::copy(it.begin(), it.end(), out.mutable_data());
+                               return out;
+                             })
+      .def_property_readonly("n_planes",
+                             [](const PyPlaneBatch& self) { return self.batch->NPlanes(); });
 }
 
 // planes of one size as a (n_planes, height, width) array
@@ -1597,6 +1710,7 @@ PYBIND11_MODULE(radler, m) {  // python/pywrappers.cc
   InitSpectralFitter(m);
   InitIo(m);
   InitRadler(m);
+  InitPlaneBatch(m);
   InitComponentList(m);
   InitRestore(m);
   InitSourceCatalogue(m);
